@@ -15,9 +15,15 @@ full pass of the hot path over the volume (scripts/pdl_inference3d.py:110-233 in
 
 Inputs are resident in HBM when the timed region starts (uint8 EM volume + planted head tensors, see
 empanada_amd/synthetic.py and DESIGN.md "Synthetic workload": the conv forward is computed and timed on every slice
-of every plane and checksummed, and checked after the timed region against a CPU forward of the same weights; the
-post-processing consumes the planted heads so that it sees a realistic object load -- random weights would give it
-an empty or degenerate segmentation).
+of every plane and checksummed, and with --full checked after the timed region against a CPU forward of the same
+weights; the post-processing consumes the planted heads so that it sees a realistic object load -- random weights
+would give it an empty or degenerate segmentation).
+
+A plain run does only what the headline figure needs: inputs, model, warm-up, the timed steps, the result line (the
+headline configuration replays the committed conv tuner choices, COMMITTED_TUNE).  `--full` adds the live tuner
+search, the forward check against the CPU and the CPU baseline leg (cpu_baseline: PQ / ids against the CPU oracle).
+`--dump-outputs DIR` writes a fixed seeded sample of what the last timed step computed (labelled volume, forward
+probabilities, checksum) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: `--gpus N` starts N ranks itself (a `torch.distributed.run` child process, before this process touches the
 GPU) unless it already runs under one (WORLD_SIZE set: the driver's launch line).  One rank per GPU, RCCL; every plane's
@@ -97,6 +103,14 @@ MODELS = {'pdl_r50': 'PanopticDeepLab/ResNet-50', 'bifpn_r50': 'PanopticBiFPN/Re
           'mitonet_pr': 'PanopticDeepLabPR/ResNet-50 = the MitoNet configuration (instance decoder, PointRend semantic '
                         'head with 2 render steps, 1/4-resolution instance heads -> step-4 grouping)'}
 MODEL_ARGS = {'mitonet_pr': (2, False)}        # forward(x, render_steps, interpolate_ins): engines.py:248-256
+# Tuner choices committed for the headline configuration (written by --save-tune on an MI355X): a plain run replays
+# them instead of the ~50 s live search (MIOpen's find + per-site timing); --full, --save-tune, --conv-impls search.
+COMMITTED_TUNE = {('orthoplane', 1024, 'pdl_r50'): os.path.join(ROOT, 'profiles', 'r3_tune_choices_ortho1024.json')}
+# --dump-outputs: sizes of the seeded samples (flat positions drawn with DUMP_SEED, sorted; everything if smaller)
+DUMP_SEED = 20260
+DUMP_LABEL_VALUES = 1 << 21                    # float64, shared by the classes: 16 MiB
+DUMP_PROB_VALUES = 1 << 20                     # float32 per plane: 4 MiB
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse():
@@ -137,6 +151,12 @@ def parse():
                          'overlap stitching"): forward per tile, per-tile post-processing, tile merge on device tables')
     ap.add_argument('--tile-overlap', type=int, default=128)
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel of the forward from Python (no HIP graph)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the live conv tuner search (instead of the '
+                         'committed choices), the forward check against a CPU forward and the CPU baseline / PQ leg')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write a fixed seeded sample of what the last step computed to '
+                         'DIR/<name>.npy (float32 / float64, at most 64 MiB in all)')
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 3 if args.mode == 'orthoplane' else 10
@@ -166,6 +186,51 @@ def log(msg):
 
 
 _T0 = time.perf_counter()
+
+
+def tune_choices(args):
+    """--load-tune file for Pipeline.tune: the one given, else the committed choices when a plain run matches the
+    configuration they were tuned on, else None (live search)"""
+    if args.load_tune or args.full or args.save_tune or args.conv_impls:
+        return args.load_tune
+    if args.things != 1 or args.dtype != 'fp32' or args.batch != 128 or args.tune_batch != 32 or args.tile:
+        return None
+    path = COMMITTED_TUNE.get((args.mode, args.size, args.model))
+    return path if path and os.path.isfile(path) else None
+
+
+def conv_choices_label(args):
+    if args.no_tune or args.dtype != 'fp32':
+        return 'miopen (not tuned)'
+    path = tune_choices(args)
+    return 'searched at warm-up' if path is None else f'replayed from {os.path.relpath(path, ROOT)}'
+
+
+def sample_index(n, device=None, m=DUMP_PROB_VALUES):
+    """fixed, seeded flat positions (sorted) into an array of n elements: all of them when n <= m"""
+    if n <= m:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=m, dtype=np.int64))
+    return torch.from_numpy(idx).to(device) if device is not None else idx
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> numpy array (float32 / float64) -> out_dir/<name>.npy"""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}'
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    log(f'outputs of the last step -> {out_dir}: {sorted(arrays)} ({total / 2 ** 20:.1f} MiB)')
+
+
+def label_sample(vol, m):
+    """seeded sample of a labelled uint32 volume (device or host) as exact float64"""
+    flat = vol.reshape(-1).view(torch.int32)
+    idx = sample_index(flat.numel(), flat.device, m)
+    return flat[idx].cpu().numpy().view(np.uint32).astype(np.float64)
 
 
 # ----------------------------------------------------------------------------------------------- model
@@ -515,7 +580,7 @@ def postprocess_planes(heads, shape3d, writer, stages, between=None, before=None
     return sum(int(cons[c].alive.sum()) for c in LABELS), vols, zs
 
 
-def orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first=None, prefetch_next=False):
+def orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first=None, prefetch_next=False, keep=None):
     """One pass.  Two HIP streams: forwards on the default stream, everything downstream of a plane's forward (pixel
     kernels, tables, chain, lift; after the third plane consensus, fill, D2H, zarr write) on the post-processing stream
     behind that forward's event.
@@ -524,7 +589,9 @@ def orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first=None, pr
     matters most when the slices are sharded over several ranks and a plane's forward is as short as its host work.
     Un-captured forwards (~11 000 launches per plane, more than the HIP queue holds) are queued one plane ahead instead:
     plane p+1 as soon as the device tables of plane p are on the host.  The caller hands the returned
-    (checksum, event) back as `first`."""
+    (checksum, event) back as `first`.
+    keep (--dump-outputs): dict that receives a seeded sample of every forward's probabilities (by plane, on the
+    forward's stream: keep['index']) and the pass's labelled volumes (keep['vols'])"""
     post = pipe.post_stream
     planes = ('xy', 'xz', 'yz')
     state = {'next': None}
@@ -533,7 +600,10 @@ def orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first=None, pr
     def launch(axis, key=None):
         key = key or axis
         with torch.cuda.stream(torch.cuda.default_stream()):
-            _, chk[key] = pipe.forward(*stacks[axis])
+            prob, chk[key] = pipe.forward(*stacks[axis])
+            if keep is not None:
+                keep[f'prob_{axis}'] = prob.view(-1)[keep['index']]
+            del prob
             ev[key] = torch.cuda.Event()
             ev[key].record()
 
@@ -561,8 +631,10 @@ def orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first=None, pr
         post.wait_event(ev[axis])
 
     with torch.cuda.stream(post):
-        n_found, _, _ = postprocess_planes(heads, shape3d, writer, stages, between, before)
+        n_found, vols, _ = postprocess_planes(heads, shape3d, writer, stages, between, before)
     torch.cuda.current_stream().wait_stream(post)
+    if keep is not None:
+        keep['vols'] = vols
     if 'next' in ev:
         state['next'] = (chk['next'], ev['next'])
     return chk['xy'] + chk['xz'] + chk['yz'], n_found, state['next']
@@ -626,9 +698,9 @@ def main_orthoplane(args, device, rank, world):
     pipe = Pipeline(args, device)
     if not args.no_tune:
         if world > 1:
-            pipe.tune_on_rank0(S, rank, args.save_tune, args.load_tune)   # every rank runs the same kernels
+            pipe.tune_on_rank0(S, rank, args.save_tune, tune_choices(args))   # every rank runs the same kernels
         else:
-            pipe.tune(S, args.save_tune, args.load_tune)
+            pipe.tune(S, args.save_tune, tune_choices(args))
     shape3d = (S, S, S)
     from empanada_amd.inference.sharded import shard_bounds
     from empanada_amd.zarr_utils import SlabWriter, ZarrV2Group, open_zarr
@@ -658,11 +730,16 @@ def main_orthoplane(args, device, rank, world):
     _hip.PROFILE = {}
     pipe.dense_profile_left = 3                      # the dense-path calls of the first pass's three forwards are timed
     stages, chks = {}, []
+    keep = None
+    if args.dump_outputs:                            # every plane's block of probabilities has the same size
+        lo, hi = stacks['xy'][2], stacks['xy'][3]
+        n_prob = (hi - lo) * (1 if len(LABELS) == 1 else len(LABELS) + 1) * S * S
+        keep = {'index': sample_index(n_prob, device)}
     t0 = time.perf_counter()
     first = None
     for k in range(args.steps):
         chk, n_found, first = orthoplane_step(pipe, stacks, heads, shape3d, writer, stages, first,
-                                              prefetch_next=(k + 1 < args.steps) and not args.no_pipeline)
+                                              prefetch_next=(k + 1 < args.steps) and not args.no_pipeline, keep=keep)
         chks.append(chk)
     for w in writer.values():
         w.drain()                                    # the last pass's chunk files are on disk
@@ -723,10 +800,17 @@ def main_orthoplane(args, device, rank, world):
         'forward_checksum': chks[-1], 'forward_checksum_stable': bool(all(c == chks[0] for c in chks)),
         'hip_calls_ms': per_call, 'hip_ms_per_pass': per_pass, 'roofline': roof,
     }
-    if not args.no_forward_check:
+    res['conv_choices'] = conv_choices_label(args)
+    if keep is not None:                             # rank 0: its z-slab of every class, its block of every plane
+        arrays = {f'labels_class{c}': label_sample(keep['vols'][c], DUMP_LABEL_VALUES // len(LABELS)) for c in LABELS}
+        arrays.update({k: v.float().cpu().numpy() for k, v in keep.items() if k.startswith('prob_')})
+        arrays['forward_checksum'] = np.array([chks[-1]], dtype=np.float64)
+        arrays['objects_found'] = np.array([n_found], dtype=np.float64)
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full and not args.no_forward_check:
         log('forward check against the CPU')
         res['forward_check'] = forward_check(args, pipe, stacks['xy'][0])
-    if not args.no_cpu_baseline and world == 1 and args.cpu_size > 0:
+    if args.full and not args.no_cpu_baseline and world == 1 and args.cpu_size > 0:
         log('cpu baseline')
         del heads
         torch.cuda.empty_cache()
@@ -865,7 +949,7 @@ def main_stack(args, device, rank, world):
         log(f'{len(pipe.tiler)} tiles of {args.tile} px, overlap >= {args.tile_overlap}')
     fwd = (lambda v: pipe.forward_tiled(v, pipe.tiler)) if args.tile else pipe.forward
     if not args.no_tune:
-        pipe.tune(args.tile or S, args.save_tune, args.load_tune)
+        pipe.tune(args.tile or S, args.save_tune, tune_choices(args))
     host_out = torch.empty((D, S, S), dtype=torch.int32).pin_memory()
 
     def barrier():
@@ -975,9 +1059,16 @@ def main_stack(args, device, rank, world):
         'forward_checksum': chks[-1], 'forward_checksum_stable': bool(all(c == chks[0] for c in chks)),
         'hip_calls_ms': per_call, 'hip_ms_per_pass': per_pass, 'roofline': roof,
     }
-    if not args.no_forward_check:
+    res['conv_choices'] = conv_choices_label(args)
+    if args.dump_outputs:                            # rank 0's labelled slab and the last forward's probabilities
+        arrays = {'labels': label_sample(host_out, DUMP_LABEL_VALUES)}
+        if prob is not None:
+            arrays['prob_xy'] = prob.reshape(-1)[sample_index(prob.numel(), prob.device)].float().cpu().numpy()
+        arrays['forward_checksum'] = np.array([chks[-1]], dtype=np.float64)
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full and not args.no_forward_check:
         res['forward_check'] = forward_check(args, pipe, vol, axes=('xy',))
-    if not args.no_cpu_baseline and world == 1 and args.cpu_slices > 0:
+    if args.full and not args.no_cpu_baseline and world == 1 and args.cpu_slices > 0:
         log('cpu baseline')
         res['cpu_baseline'] = cpu_baseline_stack(args, vol.vol, heads, args.cpu_slices, pipe)
     else:

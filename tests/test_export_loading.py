@@ -2,9 +2,6 @@
 scripts/export_model.py:182-194 writes them, and a training checkpoint as scripts/inference3d_multigpu.py:288-300 reads
 it.  The archive is treated as a container of named tensors: architecture inferred from names and shapes, this
 package's module built and loaded strictly; outputs must equal the archive's own forward."""
-import os
-import sys
-
 import pytest
 import torch
 import yaml
@@ -69,41 +66,51 @@ def test_training_checkpoint(tmp_path):
         assert torch.equal(model(x)['offsets'], m(x)['offsets'])
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/empanada'), reason='reference not present (GPU box)')
+class _Archive(torch.nn.Module):
+    """named tensors only: the state-dict layout of an archive, no code of the class it was scripted from"""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return x
+
+
+def _archive_from_layout(g, layout):
+    """tests/golden/reference_pr_archive.npz (oracle/gen_golden_layouts.py) -> a module whose state dict has the
+    reference archive's names, shapes, dtypes and order, under the reference's class name, with the weights
+    `synthesize_weights` derives from those names and shapes (as the fixture's heads were computed with)"""
+    keys, ndim, dims, dtypes = (g[f'{layout}_{k}'] for k in ('keys', 'ndim', 'dims', 'dtype'))
+    root = type(str(g[f'{layout}_class']), (_Archive,), {})()
+    at = 0
+    for key, n, dt in zip(keys, ndim, dtypes):
+        shape = tuple(int(d) for d in dims[at:at + n])
+        at += n
+        *path, leaf = str(key).split('.')
+        mod = root
+        for p in path:
+            if p not in mod._modules:
+                mod.add_module(p, _Archive())
+            mod = mod._modules[p]
+        mod.register_buffer(leaf, torch.zeros(shape, dtype=getattr(torch, str(dt))))
+    assert list(root.state_dict()) == [str(k) for k in keys]
+    return models.synthesize_weights(root)
+
+
 @pytest.mark.parametrize('layout', ['fused', 'plain'])
 def test_archive_scripted_from_the_reference_class(tmp_path, layout):
-    """build container only: the archive scripts/export_model.py writes -- the REFERENCE's
-    QuantizablePanopticDeepLabPR, `fuse_model()` applied as the script does (layout 'fused': ConvReLU2d wrappers,
-    BatchNorms folded into conv biases, 187 tensors instead of 423) or not ('plain'), scripted and saved in a scratch
-    directory (never committed) -- loads into this package's PanopticDeepLabPR and both give the same heads through
-    the exported 3-argument forward."""
-    import subprocess
-    code = r'''
-import sys
-sys.dont_write_bytecode = True
-sys.path.insert(0, %r)
-from oracle.gen_golden import _install_standins
-_install_standins()
-import warnings; warnings.filterwarnings('ignore')
-import torch
-from empanada.models.quantization import panoptic_deeplab as Q
-from empanada_amd.models import synthesize_weights
-m = synthesize_weights(Q.QuantizablePanopticDeepLabPR(encoder='resnet50', num_classes=1, quantize=False)).eval()
-if sys.argv[3] == 'fused':
-    m.fuse_model()                      # scripts/export_model.py:115-120: eval, fuse, then script
-torch.jit.save(torch.jit.script(m), sys.argv[1])
-x = torch.randn(1, 1, 96, 96, generator=torch.Generator().manual_seed(0))
-with torch.no_grad():
-    out = m(x, 2, False)
-torch.save({k: v for k, v in out.items()}, sys.argv[2])
-''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    arch_path, out_path = str(tmp_path / 'PanopticDeepLabPR_ref.pth'), str(tmp_path / 'out.pt')
-    r = subprocess.run([sys.executable, '-c', code, arch_path, out_path, layout], capture_output=True, text=True, cwd='/tmp')
-    assert r.returncode == 0, r.stderr[-3000:]
+    """the archive scripts/export_model.py writes -- the REFERENCE's QuantizablePanopticDeepLabPR (ResNet-50),
+    `fuse_model()` applied as the script does (layout 'fused': ConvReLU2d wrappers, BatchNorms folded into conv biases,
+    187 tensors instead of 423) or not ('plain') -- loads into this package's PanopticDeepLabPR and both give the same
+    heads through the exported 3-argument forward.  The archive is rebuilt from the reference's layout
+    (tests/golden/reference_pr_archive.npz: names, shapes, dtypes, class name, and the reference's heads on the stored
+    input with the weights synthesised from those names), scripted and saved in a scratch directory."""
+    from conftest import load_golden
+    g = load_golden('reference_pr_archive')
+    arch_path = str(tmp_path / 'PanopticDeepLabPR_ref.pth')
+    torch.jit.save(torch.jit.script(_archive_from_layout(g, layout)), arch_path)
     model, desc = EX.load_exported(_descriptor(tmp_path, arch_path), device='cpu', prepare=False)
     assert desc['arch'] == 'PanopticDeepLabPR' and desc['model_kwargs']['encoder'] == 'resnet50'
-    ref = torch.load(out_path, weights_only=True)
-    x = torch.randn(1, 1, 96, 96, generator=torch.Generator().manual_seed(0))
+    ref = {str(k): torch.from_numpy(g[f'{layout}_head_{k}']) for k in g[f'{layout}_heads']}
+    assert set(ref) == {'sem_logits', 'ctr_hmp', 'offsets'}
+    x = torch.from_numpy(g['x'])
     with torch.no_grad():
         out = model(x, 2, False)
     for k in ref:

@@ -1,63 +1,34 @@
-"""Build container only (the reference is not on the GPU box): the reference's own drivers resolve every name they
-take from `empanada.*`, `config_utils` and `sampler` against this repository through the `compat/` name table --
-"the script imports cleanly" of SURVEY 8(b).  The scripts are parsed, never executed or copied: their third-party
-imports (zarr, mlflow, skimage, albumentations, cv2) are absent from this image."""
-import ast
-import builtins
-import importlib
+"""The reference's own drivers resolve every name they take from `empanada.*`, `config_utils` and `sampler` against
+this repository through the `compat/` name table -- "the script imports cleanly" of SURVEY 8(b).  The scripts' name
+tables (what each imports from those modules, and what it loads without binding it itself) are a fixture,
+tests/golden/reference_scripts.npz (oracle/gen_golden_layouts.py parses the scripts; they are never executed or
+copied: their third-party imports (zarr, mlflow, skimage, albumentations, cv2) are absent from this image)."""
+import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
-REF_SCRIPTS = '/root/reference/scripts'
+from conftest import load_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OURS = ('empanada', 'config_utils', 'sampler')
 
 _CHECK = r'''
-import ast, builtins, importlib, sys
-path = sys.argv[1]
-tree = ast.parse(open(path).read())
-ours = ('empanada', 'config_utils', 'sampler')
-star, explicit, other_imports = [], {}, set()
-for node in ast.walk(tree):
-    if isinstance(node, ast.ImportFrom) and node.module and node.module.split('.')[0] in ours:
-        mod = importlib.import_module(node.module)
-        for a in node.names:
-            if a.name == '*':
-                star.append(mod)
-            else:
-                assert hasattr(mod, a.name) or importlib.util.find_spec(node.module + '.' + a.name), (node.module, a.name)
-                explicit[a.asname or a.name] = node.module
-    elif isinstance(node, ast.Import):
-        for a in node.names:
-            if a.name.split('.')[0] in ours:
-                importlib.import_module(a.name)
-            other_imports.add((a.asname or a.name).split('.')[0])
-    elif isinstance(node, ast.ImportFrom):
-        for a in node.names:
-            other_imports.add(a.asname or a.name)
+import builtins, importlib, json, sys
+t = json.loads(sys.argv[1])
+star = []
+for mod, name in zip(t['from_module'], t['from_name']):
+    m = importlib.import_module(mod)
+    if name == '*':
+        star.append(m)
+    else:
+        assert hasattr(m, name) or importlib.util.find_spec(mod + '.' + name), (mod, name)
+for mod in t['imports']:
+    importlib.import_module(mod)
 # names the script uses but never binds itself: they must come out of the star imports
-bound = set(explicit) | other_imports | set(dir(builtins))
-for node in ast.walk(tree):
-    if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
-        bound.add(node.name)
-        if isinstance(node, ast.FunctionDef):
-            for a in node.args.args + node.args.kwonlyargs:
-                bound.add(a.arg)
-            if node.args.vararg: bound.add(node.args.vararg.arg)
-            if node.args.kwarg: bound.add(node.args.kwarg.arg)
-    elif isinstance(node, ast.Name) and isinstance(node.ctx, (ast.Store, ast.Del)):
-        bound.add(node.id)
-    elif isinstance(node, ast.ExceptHandler) and node.name:
-        bound.add(node.name)
-    elif isinstance(node, ast.alias):
-        pass
-    elif isinstance(node, ast.comprehension):
-        for n in ast.walk(node.target):
-            if isinstance(n, ast.Name): bound.add(n.id)
-free = sorted({n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load)} - bound)
+free = sorted(set(t['unbound']) - set(dir(builtins)))
 exported = set()
 for m in star:
     exported |= set(getattr(m, '__all__', [k for k in vars(m) if not k.startswith('_')]))
@@ -67,7 +38,6 @@ print('MISSING', missing)
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCRIPTS), reason='reference not present (GPU box)')
 @pytest.mark.parametrize('script,allowed_missing', [
     ('pdl_inference3d.py', set()),
     # names the script itself never binds and no module of the reference defines either (bare
@@ -75,9 +45,12 @@ print('MISSING', missing)
     ('inference3d_multigpu.py', {'logging', 'get_rank', 'queue', 'snakemake'}),
 ])
 def test_reference_script_names_resolve(script, allowed_missing):
+    g, stem = load_golden('reference_scripts'), os.path.splitext(script)[0]
+    table = {k: [str(v) for v in g[f'{stem}_{k}']] for k in ('from_module', 'from_name', 'imports', 'unbound')}
+    assert table['from_module'], f'{script}: no names taken from this package in the fixture'
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'compat'), ROOT]))
-    out = subprocess.run([sys.executable, '-c', _CHECK, os.path.join(REF_SCRIPTS, script)], env=env, capture_output=True,
-                         text=True, cwd='/tmp')
+    out = subprocess.run([sys.executable, '-c', _CHECK, json.dumps(table)], env=env, capture_output=True, text=True,
+                         cwd=tempfile.gettempdir())
     assert out.returncode == 0, out.stderr[-3000:]
     missing = eval([l for l in out.stdout.splitlines() if l.startswith('MISSING')][0].split(' ', 1)[1])
     assert set(missing) <= allowed_missing, missing

@@ -24,6 +24,7 @@ pmc1024)
 mitonet)
   cd $R
   timeout -k 10 900 python bench.py --model mitonet_pr --steps 3 --cpu-size 192 --save-tune /tmp/tune_mito.json \
+    --full \
     > gpurun_out/r3_bench_ortho1024_mitonet_pr.json 2> gpurun_out/r3_bench_ortho1024_mitonet_pr.log || exit 1
   cp /tmp/tune_mito.json gpurun_out/r3_tune_choices_mitonet_pr.json
   tail -2 gpurun_out/r3_bench_ortho1024_mitonet_pr.log
@@ -38,6 +39,7 @@ final)
   # choices replayed -> timed-region summary, the post-processing in isolation, the per-slice protocol lines
   cd $R
   timeout -k 10 900 python bench.py --steps 5 --warmup 1 --save-tune gpurun_out/r3_tune_choices_ortho1024.json \
+    --full \
     > gpurun_out/r3_bench_ortho1024.json 2> gpurun_out/r3_bench_ortho1024.log || exit 1
   tail -1 gpurun_out/r3_bench_ortho1024.log
   cd /tmp
