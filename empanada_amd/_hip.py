@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(_HERE, 'libemp_hip.so')
 
 MAX_KS = 11
 MAX_CLASSES = 16
-MAX_CENTERS = 4096
+MAX_CENTERS = 4096          # default per-slice centre limit (emp_find_centers: in-LDS sort)
+CENTER_LIMIT = 65535        # hard per-slice limit (uint16 ids); emp_find_centers_ws, opt-in
 
 
 class HipError(RuntimeError):
@@ -70,6 +71,8 @@ SIGNATURES = {
     'emp_median_step': (_I, [_c.POINTER(_P), _I, _L, _P, _P]),
     'emp_harden': (_I, [_P, _I, _I, _L, _F, _P, _P]),
     'emp_find_centers': (_I, [_P, _I, _I, _I, _F, _I, _I, _P, _P, _P]),
+    'emp_find_centers_work_elems': (_L, [_I, _I, _I, _I]),
+    'emp_find_centers_ws': (_I, [_P, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P]),
     'emp_group_work_elems': (_L, [_I, _I]),
     'emp_group_pixels': (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _U32, _P, _P, _P]),
     'emp_fuse_work_elems': (_L, [_I, _I, _I]),
@@ -258,6 +261,27 @@ def find_centers(hmp, thr, k, cap=1024):
     idx = torch.empty((D, cap), dtype=torch.int32, device=hmp.device)
     cnt = torch.empty((D,), dtype=torch.int32, device=hmp.device)
     call('emp_find_centers', _ptr(hmp), D, h, w, float(thr), int(k), int(cap), _ptr(idx), _ptr(cnt), stream())
+    return idx, cnt
+
+
+def find_centers_ws(hmp, thr, k, cap):
+    """find_centers for any capacity 1..CENTER_LIMIT: hmp (D,h,w) fp32 -> idx (D,cap) int32, count (D) int32.
+    count is exact; idx holds the first min(count, cap) centres of each slice in raster order."""
+    require_gpu()
+    _expect("find_centers_ws: heat map", hmp, torch.float32)
+    D, h, w = hmp.shape
+    hmp = hmp.contiguous()
+    cap = int(cap)
+    if not 1 <= cap <= CENTER_LIMIT:
+        raise HipError(f"find_centers_ws: cap {cap} not in 1..{CENTER_LIMIT}")
+    idx = torch.empty((D, cap), dtype=torch.int32, device=hmp.device)
+    cnt = torch.empty((D,), dtype=torch.int32, device=hmp.device)
+    n_work = query('emp_find_centers_work_elems', D, h, w, cap)
+    if n_work <= 0:
+        raise HipError(f"find_centers_ws: bad shape {tuple(hmp.shape)}")
+    work = torch.empty((n_work,), dtype=torch.int32, device=hmp.device)
+    call('emp_find_centers_ws', _ptr(hmp), D, h, w, float(thr), int(k), cap, _ptr(work), _ptr(idx), _ptr(cnt),
+         stream())
     return idx, cnt
 
 

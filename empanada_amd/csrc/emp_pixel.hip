@@ -355,7 +355,10 @@ __device__ __forceinline__ bool is_window_max(const float *__restrict__ img, int
     return !(m > v);
 }
 
-template <int VEC>
+// BITMAP = false: a centre takes the next free slot of out_idx (D, cap) -- arrival order, sorted afterwards in LDS
+// (sort_centers_kernel, cap <= EMP_MAX_CENTERS).  BITMAP = true (emp_find_centers_ws): out_idx is the per-slice bitmap
+// (D, cap) of 32-bit words, cap = words per slice, and a centre sets bit (y*w + x) of its slice; out_count is not touched.
+template <int VEC, bool BITMAP>
 __global__ __launch_bounds__(256) void find_centers_kernel(const float *__restrict__ hmp, int h, int w, float thr,
                                                            int k, int cap, int32_t *__restrict__ out_idx,
                                                            int32_t *__restrict__ out_count)
@@ -471,8 +474,13 @@ __global__ __launch_bounds__(256) void find_centers_kernel(const float *__restri
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
                     if (lane == src && !(m > cv)) {
-                        int slot = atomicAdd(&out_count[d], 1);
-                        if (slot < cap) out_idx[(int64_t)d * cap + slot] = cy * w + cx;
+                        if constexpr (BITMAP) {
+                            const uint32_t q = (uint32_t)cy * (uint32_t)w + (uint32_t)cx;        // < h*w <= 32 * cap
+                            atomicOr(reinterpret_cast<uint32_t *>(out_idx) + (int64_t)d * cap + (q >> 5), 1u << (q & 31u));
+                        } else {
+                            int slot = atomicAdd(&out_count[d], 1);
+                            if (slot < cap) out_idx[(int64_t)d * cap + slot] = cy * w + cx;
+                        }
                     }
                 }
             }
@@ -526,16 +534,127 @@ extern "C" int emp_find_centers(const float *hmp, int D, int h, int w, float thr
         // 64 float4 per lane = 16 trips of the 4-load loop: few, long-lived blocks (one trip per lane: 1.52 ms per
         // 1024^3 plane, 16 trips: 1.27 ms)
         int gx = emp_grid(emp_cdiv(hw / 4, 64), 256, 512);
-        hipLaunchKernelGGL(find_centers_kernel<4>, dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, cap, out_idx,
-                           out_count);
+        hipLaunchKernelGGL((find_centers_kernel<4, false>), dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, cap,
+                           out_idx, out_count);
     } else {
         int gx = emp_grid(emp_cdiv(hw, 4), 256, 1024);
-        hipLaunchKernelGGL(find_centers_kernel<1>, dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, cap, out_idx,
-                           out_count);
+        hipLaunchKernelGGL((find_centers_kernel<1, false>), dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, cap,
+                           out_idx, out_count);
     }
     EMP_CHECK_LAUNCH("emp_find_centers");
     hipLaunchKernelGGL(sort_centers_kernel, dim3(D), dim3(256), 0, st, out_idx, out_count, cap);
     EMP_CHECK_LAUNCH("emp_find_centers(sort)");
+    return EMP_OK;
+}
+
+// P3, any capacity up to EMP_CENTER_LIMIT (emp_find_centers_ws).  The sort above holds a slice's centres in LDS, which
+// ends at EMP_MAX_CENTERS.  Here the NMS kernel marks every centre in a per-slice bitmap (one bit per pixel, 1/32 of
+// the heat map), and one block per slice walks the bitmap in order: raster order by construction, no sort, and the
+// first `cap` centres are kept when a slice overflows.  Traffic on top of the 4 B/pixel of the NMS: the bitmap is
+// written once (zeroing) and read once, 0.25 B/pixel, plus 4 B per centre.
+#define CB_THREADS 1024
+#define CB_WORDS 4                 // bitmap words per thread and trip: one 16-byte load
+
+// words per slice: a multiple of CB_WORDS, so that every slice's bitmap starts on a 16-byte boundary
+static inline int64_t centers_bitmap_words(int64_t hw) { return emp_cdiv(emp_cdiv(hw, 32), CB_WORDS) * CB_WORDS; }
+
+// a kernel, not a memset node: DESIGN section 9
+__global__ __launch_bounds__(256) void centers_bitmap_zero_kernel(uint4 *__restrict__ bitmap4, int64_t n4)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+        bitmap4[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(CB_THREADS) void centers_from_bitmap_kernel(const uint32_t *__restrict__ bitmap, int nw,
+                                                                         int cap, int32_t *__restrict__ out_idx,
+                                                                         int32_t *__restrict__ out_count)
+{
+    __shared__ int wave_sum[CB_THREADS / 64];
+    const int d = blockIdx.x;
+    const uint32_t *bm = bitmap + (int64_t)d * nw;
+    int32_t *out = out_idx + (int64_t)d * cap;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int running = 0;                                           // centres before this trip (block-uniform)
+    for (int base = 0; base < nw; base += CB_THREADS * CB_WORDS) {         // block-uniform trip count
+        const int wi = base + (int)threadIdx.x * CB_WORDS;                 // nw % CB_WORDS == 0: wi < nw covers 4 words
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (wi < nw) v = *reinterpret_cast<const uint4 *>(bm + wi);
+        const uint32_t word[CB_WORDS] = {v.x, v.y, v.z, v.w};
+        int mine = 0;
+#pragma unroll
+        for (int j = 0; j < CB_WORDS; ++j) mine += __popc(word[j]);
+        int incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            int t = __shfl_up(incl, o);
+            if (lane >= o) incl += t;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int i = 0; i < CB_THREADS / 64; ++i) {
+            const int s = wave_sum[i];
+            before += (i < wave) ? s : 0;
+            total += s;
+        }
+        int pos = running + before + incl - mine;
+        if (mine && pos < cap) {
+#pragma unroll
+            for (int j = 0; j < CB_WORDS; ++j) {
+                uint32_t bits = word[j];
+                while (bits) {
+                    const int b = __ffs((int)bits) - 1;
+                    bits &= bits - 1;
+                    if (pos < cap) out[pos] = (wi + j) * 32 + b;
+                    ++pos;
+                }
+            }
+        }
+        running += total;
+        __syncthreads();                                       // wave_sum is rewritten by the next trip
+    }
+    if (threadIdx.x == 0) out_count[d] = running;
+}
+
+extern "C" int64_t emp_find_centers_work_elems(int D, int h, int w, int cap)
+{
+    (void)cap;                                                 // the bitmap does not depend on the capacity
+    if (h <= 0 || w <= 0 || (int64_t)h * w >= (1LL << 31)) return 0;
+    return (int64_t)(D > 0 ? D : 1) * centers_bitmap_words((int64_t)h * w);
+}
+
+extern "C" int emp_find_centers_ws(const float *hmp, int D, int h, int w, float thr, int k, int cap, int32_t *work,
+                                   int32_t *out_idx, int32_t *out_count, void *stream)
+{
+    EMP_REQUIRE(hmp && work && out_idx && out_count, "find_centers_ws: null pointer");
+    EMP_REQUIRE(k >= 1 && k <= CT_MAXK, "find_centers_ws: nms kernel %d not in 1..%d", k, CT_MAXK);
+    EMP_REQUIRE(cap >= 1 && cap <= EMP_CENTER_LIMIT, "find_centers_ws: cap %d not in 1..%d", cap, EMP_CENTER_LIMIT);
+    EMP_REQUIRE(D >= 0 && D <= 65535 && h > 0 && w > 0, "find_centers_ws: bad shape D=%d h=%d w=%d", D, h, w);
+    EMP_REQUIRE((int64_t)h * w < (1LL << 31), "find_centers_ws: slice too large");
+    EMP_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0, "find_centers_ws: work must be 16-byte aligned");
+    if (D == 0) return EMP_OK;
+    hipStream_t st = emp_stream(stream);
+    const int64_t hw = (int64_t)h * w;
+    const int nw = (int)centers_bitmap_words(hw);
+    const int64_t n4 = (int64_t)D * nw / CB_WORDS;
+    hipLaunchKernelGGL(centers_bitmap_zero_kernel, dim3(emp_grid(n4, 256, 2048)), dim3(256), 0, st,
+                       reinterpret_cast<uint4 *>(work), n4);
+    EMP_CHECK_LAUNCH("emp_find_centers_ws(zero)");
+    const bool vec4 = (w % 4 == 0) && ((reinterpret_cast<uintptr_t>(hmp) & 15) == 0);
+    if (vec4) {
+        int gx = emp_grid(emp_cdiv(hw / 4, 64), 256, 512);                 // same grids as emp_find_centers
+        hipLaunchKernelGGL((find_centers_kernel<4, true>), dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, nw, work,
+                           out_count);
+    } else {
+        int gx = emp_grid(emp_cdiv(hw, 4), 256, 1024);
+        hipLaunchKernelGGL((find_centers_kernel<1, true>), dim3(gx, D), dim3(256), 0, st, hmp, h, w, thr, k, nw, work,
+                           out_count);
+    }
+    EMP_CHECK_LAUNCH("emp_find_centers_ws");
+    hipLaunchKernelGGL(centers_from_bitmap_kernel, dim3(D), dim3(CB_THREADS), 0, st,
+                       reinterpret_cast<const uint32_t *>(work), nw, cap, out_idx, out_count);
+    EMP_CHECK_LAUNCH("emp_find_centers_ws(extract)");
     return EMP_OK;
 }
 
@@ -795,7 +914,9 @@ extern "C" int emp_group_pixels(const int32_t *ctr_idx, const int32_t *ctr_count
 {
     EMP_REQUIRE(ctr_idx && ctr_count && offsets && out_ids && work, "group_pixels: null pointer");
     EMP_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7) == 0, "group_pixels: work must be 8-byte aligned");
-    EMP_REQUIRE(cap >= 1 && cap <= EMP_MAX_CENTERS, "group_pixels: cap %d not in 1..%d", cap, EMP_MAX_CENTERS);
+    // candidate indices and ids are uint16: index <= 65534, padding entry (uint16_t)K <= 65535 < cap + 2 * GP_BATCH,
+    // id = index + 1 <= 65535
+    EMP_REQUIRE(cap >= 1 && cap <= EMP_CENTER_LIMIT, "group_pixels: cap %d not in 1..%d", cap, EMP_CENTER_LIMIT);
     EMP_REQUIRE(step == 1 || step == 4, "group_pixels: step must be 1 or 4");
     EMP_REQUIRE(D >= 0 && D <= 65535 && h > 0 && w > 0, "group_pixels: bad shape");
     EMP_REQUIRE((int64_t)h * step < (1 << 24) && (int64_t)w * step < (1 << 24), "group_pixels: coords exceed fp32 integers");

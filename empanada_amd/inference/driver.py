@@ -66,7 +66,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     params = dict(thing_list=thing_list, label_divisor=div, stuff_area=engine.stuff_area, void_label=engine.void_label,
                   nms_threshold=engine.nms_threshold, nms_kernel=engine.nms_kernel,
                   confidence_thr=engine.confidence_thr, median_kernel_size=getattr(engine, 'ks', 1),
-                  coarse_boundaries=bool(getattr(engine, 'coarse_boundaries', False)))
+                  coarse_boundaries=bool(getattr(engine, 'coarse_boundaries', False)),
+                  max_centers=getattr(engine, 'max_centers', None))
     planes, base = {}, 0
     for axis in axes:
         n = dv.n_slices(axis)

@@ -133,6 +133,8 @@ class PanopticDeepLabEngine(_Engine):
         self.stuff_area, self.void_label = stuff_area, void_label
         self.nms_threshold, self.nms_kernel = nms_threshold, nms_kernel
         self.confidence_thr = confidence_thr
+        # per-slice centre limit (postprocess.centers_batched); None: EMP_MAX_CENTERS in the environment, default 4096
+        self.max_centers = kwargs.get('max_centers')
 
     @torch.no_grad()
     def _harden_seg(self, sem):
@@ -157,7 +159,8 @@ class PanopticDeepLabEngine(_Engine):
     @torch.no_grad()
     def postprocess(self, sem, ctr_hmp, offsets):
         return get_panoptic_segmentation(sem, ctr_hmp, offsets, self.thing_list, self.label_divisor, self.stuff_area,
-                                         self.void_label, self.nms_threshold, self.nms_kernel)[0]
+                                         self.void_label, self.nms_threshold, self.nms_kernel,
+                                         max_centers=self.max_centers)[0]
 
     def _stack_form_ok(self, heads):
         """one slice through the whole-stack kernels (postprocess.panoptic_stack with a median of 1: five launch groups,
@@ -189,7 +192,8 @@ class PanopticDeepLabEngine(_Engine):
     def _stack_params(self):
         return dict(thing_list=self.thing_list, label_divisor=self.label_divisor, stuff_area=self.stuff_area,
                     void_label=self.void_label, nms_threshold=self.nms_threshold, nms_kernel=self.nms_kernel,
-                    confidence_thr=self.confidence_thr, median_kernel_size=getattr(self, 'ks', 1))
+                    confidence_thr=self.confidence_thr, median_kernel_size=getattr(self, 'ks', 1),
+                    max_centers=self.max_centers)
 
     @torch.no_grad()
     def forward_stack(self, images, batch_size=16, model_args=()):
@@ -260,7 +264,7 @@ class PanopticDeepLabRenderEngine(PanopticDeepLabEngine):
                  nms_kernel=7, confidence_thr=0.5, padding_factor=16, coarse_boundaries=True, **kwargs):
         super().__init__(model=model, thing_list=thing_list, label_divisor=label_divisor, stuff_area=stuff_area,
                          void_label=void_label, nms_threshold=nms_threshold, nms_kernel=nms_kernel,
-                         confidence_thr=confidence_thr)
+                         confidence_thr=confidence_thr, **kwargs)
         self.padding_factor = padding_factor
         self.coarse_boundaries = coarse_boundaries
 
@@ -276,7 +280,7 @@ class PanopticDeepLabRenderEngine(PanopticDeepLabEngine):
         neighbour to the resolution of the semantic map -> (1,1,H,W) fp32 ids, 0 everywhere without centres
         (engines.py:257-275)."""
         step = 4 if self.coarse_boundaries else 1
-        centres = find_instance_center(ctr_hmp, self.nms_threshold, self.nms_kernel)
+        centres = find_instance_center(ctr_hmp, self.nms_threshold, self.nms_kernel, max_centers=self.max_centers)
         if centres.size(0) > 0:
             cells = group_pixels(centres, offsets, step=step).float()[None]
         else:
@@ -338,7 +342,7 @@ class PanopticDeepLabRenderEngine3d(_MedianQueue, PanopticDeepLabRenderEngine):
         super().__init__(model=model, thing_list=thing_list, label_divisor=label_divisor, stuff_area=stuff_area,
                          void_label=void_label, nms_threshold=nms_threshold, nms_kernel=nms_kernel,
                          confidence_thr=confidence_thr, median_kernel_size=median_kernel_size,
-                         padding_factor=padding_factor, coarse_boundaries=coarse_boundaries)
+                         padding_factor=padding_factor, coarse_boundaries=coarse_boundaries, **kwargs)
         self._init_deferred(deferred, deferred_batch)
 
     def __call__(self, image, size, upsampling=1):

@@ -261,13 +261,13 @@ def _cluster_rle_segs(st, ln, run_cl, n_cl, kept, new_id, cl_of, cl_seg, node, l
 
 
 def tiled_panoptic_stack(tile_heads, n_slices, tiler, labels, *, thing_list, label_divisor=1000, use_overlap=True,
-                         return_rle=False, on_single_run='raise', **engine_kwargs):
+                         return_rle=False, on_single_run='raise', max_centers=None, **engine_kwargs):
     """Panoptic labels of D slices of a tiled plane.
 
     tile_heads(i) -> {'sem' (D, C, th, tw) probabilities, 'ctr_hmp' (D, 1, h, w), 'offsets' (D, 2, h, w)} of tile i
     over all D slices (the model forward on the tile's crops, or crops of resident head tensors).
     engine_kwargs: panoptic_stack's (stuff_area, void_label, nms_threshold, nms_kernel, confidence_thr,
-    median_kernel_size, coarse_boundaries).
+    median_kernel_size, coarse_boundaries).  max_centers: per-slice (per-tile) centre limit (postprocess.centers_batched).
     Returns pan (D, H, W) uint32 on the device (and the per-slice stitched rle_segs if return_rle)."""
     _hip.require_gpu()
     import time
@@ -278,7 +278,7 @@ def tiled_panoptic_stack(tile_heads, n_slices, tiler, labels, *, thing_list, lab
     for i in range(len(tiler)):
         h = tile_heads(i)
         pan, emitted = panoptic_stack(h['sem'], h['ctr_hmp'], h['offsets'], thing_list=thing_list,
-                                      label_divisor=label_divisor, **engine_kwargs)
+                                      label_divisor=label_divisor, max_centers=max_centers, **engine_kwargs)
         assert len(emitted) == n_slices, "stack shorter than the median kernel"
         th, tw = tiler.yranges[i][1] - tiler.yranges[i][0], tiler.xranges[i][1] - tiler.xranges[i][0]
         # objects = (slice, value) groups: pan_seg_to_rle_seg(force_connected=False), tests/test_tiling.py:36-38

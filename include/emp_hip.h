@@ -36,6 +36,7 @@ extern "C" {
 #define EMP_MAX_KS 11       /* median kernel sizes 1,3,...,11 (reference: scripts/pdl_inference3d.py:28) */
 #define EMP_MAX_CLASSES 16  /* semantic channels C, and class ids < 16 */
 #define EMP_MAX_CENTERS 4096 /* per-slice centre capacity the in-LDS sort supports */
+#define EMP_CENTER_LIMIT 65535 /* hard per-slice centre limit: ids and candidate lists are uint16 */
 
 int emp_version(void);
 const char *emp_last_error(void);
@@ -296,6 +297,19 @@ int emp_harden(const float *prob, int D, int C, int64_t HW, float thr, uint8_t *
 int emp_find_centers(const float *hmp, int D, int h, int w, float thr, int k, int cap,
                      int32_t *out_idx, int32_t *out_count, void *stream);
 
+/* The same detection for any capacity 1 <= cap <= EMP_CENTER_LIMIT (no in-LDS sort)
+ * replaces find_instance_center                    empanada/inference/postprocess.py:38-76
+ * Same rule as emp_find_centers.  The centres of a slice are marked in a bitmap (one bit per pixel)
+ * and written out in one ordered pass, so
+ *   out_count (D) int32 = exact number found, whatever cap is;
+ *   out_idx (D, cap) int32 = the FIRST min(count, cap) centres of each slice in raster order
+ *   (deterministic on overflow too; entries past that are left unwritten).
+ * work: emp_find_centers_work_elems(D, h, w, cap) int32 elements, 16-byte aligned (zeroed by the call;
+ * D * ceil(h*w / 32) rounded up to 4 words per slice; 0 is returned for an invalid shape).          */
+int64_t emp_find_centers_work_elems(int D, int h, int w, int cap);
+int emp_find_centers_ws(const float *hmp, int D, int h, int w, float thr, int k, int cap, int32_t *work,
+                        int32_t *out_idx, int32_t *out_count, void *stream);
+
 /* ---- P4: nearest-centre pixel grouping -----------------------------------------------------
  * replaces group_pixels / chunked_pixel_grouping   postprocess.py:78-169
  * offsets (D, 2, h, w) fp32 (dy, dx) in full-resolution pixel units; step = 1 or 4.
@@ -303,6 +317,7 @@ int emp_find_centers(const float *hmp, int D, int h, int w, float thr, int k, in
  *      d = sqrtf(fmaf(dx, dx, dy*dy)),  dy = step*cy - (step*y + off_y), dx likewise
  * (the rounding torch.norm performs on the reference's CPU path); when K > 20 a pixel whose
  * every d >= 1e5 keeps id 0 (chunked path, :97-111).  K = min(count, cap); K == 0 -> ids 0.
+ * 1 <= cap <= EMP_CENTER_LIMIT (ids are uint16: the largest id is 65535); the centres may come in any order.
  * sem (D, h, w) u8 or NULL: when given (same resolution as the offsets), pixels whose class bit is
  * clear in thing_mask are not voted on and get id 0 -- every consumer multiplies the ids by the
  * thing mask anyway (postprocess.py:221, engines.py:280-285), so results downstream are unchanged.
