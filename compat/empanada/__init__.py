@@ -16,6 +16,8 @@ _RENAMED = {
     'empanada.config_loaders': 'empanada_amd.config_utils',          # load_config, read_yaml
     'empanada.data': 'empanada_amd.data',                            # VolumeDataset
     'empanada.data.volume_dataset': 'empanada_amd.data',
+    'empanada.data.utils': 'empanada_amd.data',                      # resize_by_factor
+    'empanada.data.utils.transforms': 'empanada_amd.data',
     'empanada.evaluation.evaluator': 'empanada_amd.evaluation',
 }
 

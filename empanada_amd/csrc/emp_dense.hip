@@ -355,6 +355,85 @@ extern "C" int emp_slices_to_input(const uint8_t *vol, int64_t stride_slice, int
     return EMP_OK;
 }
 
+// D0 with in-plane down-sampling (the reference's VolumeDataset(scale=N): cv2.resize before Normalize).  The same
+// gather, but every output pixel is first resized to a uint8 VALUE in integers -- either the 2x2 area form
+// ((s00 + s01 + s10 + s11 + 2) >> 2) or the separable 11-bit fixed-point bilinear form with the per-row / per-column
+// source offsets and coefficient pairs the host computed -- and then normalised and padded exactly like above.
+// Offsets are clamped to the plane, so a wrong table can give wrong values but never an out-of-bounds read.
+__global__ __launch_bounds__(256) void slices_to_input_scaled_kernel(
+    const uint8_t *__restrict__ vol, int64_t s_slice, int64_t s_row, int64_t s_col, int n, int h, int w, int dh, int dw,
+    int hp, int wp, const int32_t *__restrict__ row_off, const int16_t *__restrict__ row_coef,
+    const int32_t *__restrict__ col_off, const int16_t *__restrict__ col_coef, int area, float mean255,
+    float inv_std255, float *__restrict__ out)
+{
+    const int wq = (wp + 3) >> 2;
+    const int64_t total = (int64_t)n * hp * wq;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c0 = (int)(i % wq) * 4;
+        const int64_t q = i / wq;
+        const int r = (int)(q % hp);
+        const int64_t s = q / hp;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (r < dh) {
+            const uint8_t *base = vol + s * s_slice;
+            if (area) {
+                const uint8_t *p0 = base + (int64_t)(2 * r) * s_row, *p1 = p0 + s_row;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c0 + j < dw) {
+                        const int64_t x0 = (int64_t)(2 * (c0 + j)) * s_col, x1 = x0 + s_col;
+                        const int u = ((int)p0[x0] + (int)p0[x1] + (int)p1[x0] + (int)p1[x1] + 2) >> 2;
+                        v[j] = __fmul_rn(__fsub_rn((float)u, mean255), inv_std255);
+                    }
+            } else {
+                const int y0 = min(max(row_off[r], 0), h - 1), y1 = min(y0 + 1, h - 1);
+                const int b0 = row_coef[2 * r], b1 = row_coef[2 * r + 1];
+                const uint8_t *p0 = base + (int64_t)y0 * s_row, *p1 = base + (int64_t)y1 * s_row;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c0 + j < dw) {
+                        const int xa = min(max(col_off[c0 + j], 0), w - 1), xb = min(xa + 1, w - 1);
+                        const int a0 = col_coef[2 * (c0 + j)], a1 = col_coef[2 * (c0 + j) + 1];
+                        const int64_t x0 = (int64_t)xa * s_col, x1 = (int64_t)xb * s_col;
+                        const int r0 = (int)p0[x0] * a0 + (int)p0[x1] * a1;
+                        const int r1 = (int)p1[x0] * a0 + (int)p1[x1] * a1;
+                        const int u = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+                        v[j] = __fmul_rn(__fsub_rn((float)u, mean255), inv_std255);
+                    }
+            }
+        }
+        float *dst = out + (s * hp + r) * (int64_t)wp + c0;
+        if (c0 + 3 < wp && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+            *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c0 + j < wp) dst[j] = v[j];
+        }
+    }
+}
+
+extern "C" int emp_slices_to_input_scaled(const uint8_t *vol, int64_t stride_slice, int64_t stride_row,
+                                          int64_t stride_col, int n_slices, int h, int w, int dh, int dw, int hp,
+                                          int wp, const int32_t *row_off, const int16_t *row_coef,
+                                          const int32_t *col_off, const int16_t *col_coef, int area, float mean255,
+                                          float inv_std255, float *out, void *stream)
+{
+    EMP_REQUIRE(vol && out, "slices_to_input_scaled: null pointer");
+    EMP_REQUIRE(row_off && row_coef && col_off && col_coef, "slices_to_input_scaled: null table");
+    EMP_REQUIRE(n_slices >= 0 && h > 0 && w > 0, "slices_to_input_scaled: bad shape");
+    EMP_REQUIRE(dh >= 1 && dh <= h && dw >= 1 && dw <= w, "slices_to_input_scaled: destination size outside [1, source]");
+    EMP_REQUIRE(hp >= dh && wp >= dw, "slices_to_input_scaled: padded size below the destination size");
+    EMP_REQUIRE(!area || (h == 2 * dh && w == 2 * dw), "slices_to_input_scaled: the area form needs exact halving");
+    if (n_slices == 0) return EMP_OK;
+    const int64_t total = (int64_t)n_slices * hp * ((wp + 3) / 4);
+    hipLaunchKernelGGL(slices_to_input_scaled_kernel, dim3(emp_grid(total, 256, 16384)), dim3(256), 0,
+                       emp_stream(stream), vol, stride_slice, stride_row, stride_col, n_slices, h, w, dh, dw, hp, wp,
+                       row_off, row_coef, col_off, col_coef, area, mean255, inv_std255, out);
+    EMP_CHECK_LAUNCH("emp_slices_to_input_scaled");
+    return EMP_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // D6: 1x1 convolution to a few output channels (the last layer of every head: 256 -> 1 or 2, bias).  Pure streaming:
 // one wave per pixel, lane l holds the channel groups l, l + 64, ... (float4 each) and the matching weights in

@@ -27,9 +27,11 @@ _AXES = {'xy': 0, 'xz': 1, 'yz': 2}
 @torch.no_grad()
 def _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps):
     """model forward over slices [lo, hi) of one plane -> resident {'sem' probabilities, 'ctr_hmp', 'offsets'} at the
-    padded size (the reference pads every slice to a multiple of padding_factor and crops the labels, engines.py:351-394)"""
+    padded size (the reference pads every slice to a multiple of padding_factor and crops the labels, engines.py:351-394).
+    With a down-sampling volume (dv.scale = f > 1, render_steps = 2 + log2 f) the semantic head comes out at f x the
+    padded input, so the slices per call are sized by the output pixels: batch_pixels keeps bounding the memory"""
     hp, wp = dv.padded_shape(axis)
-    per = max(1, batch_pixels // (hp * wp))
+    per = max(1, batch_pixels // (hp * wp * dv.scale ** 2))
     render = hasattr(engine, 'coarse_boundaries')                      # the PointRend ("render") engines
     outs = {'sem': [], 'ctr_hmp': [], 'offsets': []}
     for s in range(lo, hi, per):
@@ -46,13 +48,17 @@ def _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps):
 
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
-                 out=None, batch_pixels=32 * 1024 * 1024, render_steps=2, group=None):
+                 out=None, batch_pixels=32 * 1024 * 1024, render_steps=2, group=None, downsample_f=1):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
     labels: all class ids; engine.thing_list says which are instance classes.  out: ZarrV2Group (or anything with the
     same create_dataset) -- one dataset '<class name>_pred' per class, uint32 for thing classes and uint8 for stuff,
     chunks (1, Y, X) (pdl_inference3d.py:225-233); rank 0 creates them, every rank writes its slab.
+    downsample_f: the script's -downsample-f (pdl_inference3d.py:50,154,169,178), a power of two: every slice is shrunk
+    in-plane by f before the model sees it (DeviceVolume(scale=f)), the semantic head is rendered with log2 f more
+    PointRend steps, the instance cells are enlarged by f more, and the labels come out at the full (D, H, W).  Needs
+    a Render engine; a DeviceVolume passed in must have been built with scale=f.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -60,21 +66,34 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     thing_list = list(engine.thing_list)
     div = engine.label_divisor
     factor = int(getattr(engine, 'padding_factor', 16))
-    dv = volume if isinstance(volume, DeviceVolume) else DeviceVolume(volume, norms['mean'], norms['std'], factor,
-                                                                      next(engine.model.parameters()).device)
+    f = downsample_f
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f < 1 or f & (f - 1):
+        raise ValueError(f"downsample_f must be a power of two >= 1, got {downsample_f!r}")
+    f = int(f)
+    if f > 1 and not hasattr(engine, 'coarse_boundaries'):
+        raise ValueError("downsample_f > 1 needs a Render engine (PanopticDeepLabRenderEngine3d: model(x, render_steps, "
+                         "interpolate_ins) and `upsampling`); the plain engines cannot render the labels back to full "
+                         f"resolution, got {type(engine).__name__}")
+    if isinstance(volume, DeviceVolume):
+        dv = volume
+        if dv.scale != f:
+            raise ValueError(f"the DeviceVolume was built with scale={dv.scale}, downsample_f={f}")
+    else:
+        dv = DeviceVolume(volume, norms['mean'], norms['std'], factor, next(engine.model.parameters()).device, scale=f)
+    steps = render_steps + f.bit_length() - 1
     shape3d = dv.shape
     params = dict(thing_list=thing_list, label_divisor=div, stuff_area=engine.stuff_area, void_label=engine.void_label,
                   nms_threshold=engine.nms_threshold, nms_kernel=engine.nms_kernel,
                   confidence_thr=engine.confidence_thr, median_kernel_size=getattr(engine, 'ks', 1),
                   coarse_boundaries=bool(getattr(engine, 'coarse_boundaries', False)),
-                  max_centers=getattr(engine, 'max_centers', None))
+                  max_centers=getattr(engine, 'max_centers', None), upsampling=f)
     planes, base = {}, 0
     for axis in axes:
         n = dv.n_slices(axis)
         b = sharded.shard_bounds(n, world)
         lo, hi = int(b[rank]), int(b[rank + 1])
         h, w = dv.plane_shape(axis)
-        heads = _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps)
+        heads = _plane_heads(engine, dv, axis, lo, hi, batch_pixels, steps)
         pan = sharded.sharded_panoptic_stack(heads['sem'], heads['ctr_hmp'], heads['offsets'], group=group, **params)
         del heads
         pan = pan[:, :h, :w].contiguous()

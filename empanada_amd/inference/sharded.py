@@ -287,9 +287,10 @@ def median_handover(prob_local, ks, thr, group=None, median=None):
 def sharded_panoptic_stack(sem_prob_local, ctr_hmp_local, offsets_local, *, thing_list, label_divisor=1000,
                            stuff_area=64, void_label=0, nms_threshold=0.1, nms_kernel=7, confidence_thr=0.5,
                            median_kernel_size=3, coarse_boundaries=True, n_classes=None, group=None,
-                           max_centers=None):
+                           max_centers=None, upsampling=1):
     """panoptic_stack for a rank's block of slices (blocks may differ in size).  Returns pan (D_local, Hp, Wp) uint32.
-    max_centers: per-slice centre limit (postprocess.centers_batched)."""
+    max_centers: per-slice centre limit (postprocess.centers_batched).  upsampling: as in panoptic_stack -- the
+    semantic map is `upsampling` x the model input, the instance cells are enlarged by step * upsampling."""
     D, C, Hp, Wp = sem_prob_local.shape
     ks = int(median_kernel_size)
     rank, world = _world(group)
@@ -299,11 +300,11 @@ def sharded_panoptic_stack(sem_prob_local, ctr_hmp_local, offsets_local, *, thin
     step = 4 if coarse_boundaries else 1
     idx, cnt = centers_batched(ctr_hmp_local, nms_threshold, nms_kernel, max_centers)
     ids = _hip.group_pixels(idx, cnt, offsets_local.float().contiguous(), step,
-                            sem=sem if step == 1 else None, thing_list=thing_list)
+                            sem=sem if (step == 1 and upsampling == 1) else None, thing_list=thing_list)
     if n_classes is None:
         n_classes = max(2 if C == 1 else C, max(thing_list) + 1)
     return _hip.fuse_panoptic(sem, ids, idx.shape[1], n_classes, thing_list, label_divisor, stuff_area, void_label,
-                              up=step)
+                              up=int(step * upsampling))
 
 
 def sharded_tables(pan_local, labels, thing_list, label_divisor, group=None):

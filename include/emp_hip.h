@@ -54,6 +54,26 @@ int emp_slices_to_input(const uint8_t *vol, int64_t stride_slice, int64_t stride
                         int n_slices, int h, int w, int hp, int wp, float mean255, float inv_std255,
                         float *out, void *stream);
 
+/* ---- D0 with in-plane down-sampling: uint8 volume -> resized, normalised, zero-padded fp32 input ----
+ * replaces VolumeDataset(scale = N).__getitem__: resize_by_factor (cv2.resize to (ceil(w/N), ceil(h/N)), default
+ *          interpolation), then Normalize and factor_pad
+ *          empanada/data/volume_dataset.py:45-51, empanada/data/utils/transforms.py:9-21
+ * vol, the strides, n_slices, (h, w), mean255, inv_std255, out and stream as in emp_slices_to_input.  (dh, dw): the
+ * resized plane, 1 <= dh <= h, 1 <= dw <= w; out is (n_slices, 1, hp, wp) with hp >= dh, wp >= dw, rows >= dh and
+ * columns >= dw zero.  The resize is integer arithmetic on tables the host computes once per (source, destination)
+ * length (empanada_amd.data.resize_tables; the fp32 coefficient arithmetic is never done on the device):
+ *   row_off (dh) int32, row_coef (dh, 2) int16: first source row y0 and the 11-bit weights (b0, b1) of rows y0 and
+ *   min(y0 + 1, h - 1);  col_off (dw) int32, col_coef (dw, 2) int16: the same for columns (a0, a1).
+ *   area == 0:  r[y] = src[y][x0] * a0 + src[y][x1] * a1  (int32)
+ *               u = (((b0 * (r[y0] >> 4)) >> 16) + ((b1 * (r[y1] >> 4)) >> 16) + 2) >> 2
+ *   area != 0 (needs h == 2 dh and w == 2 dw, the tables are not read):
+ *               u = (src[2r][2c] + src[2r][2c+1] + src[2r+1][2c] + src[2r+1][2c+1] + 2) >> 2
+ * and out = ((float)u - mean255) * inv_std255.  Table offsets are clamped to the plane on the device.             */
+int emp_slices_to_input_scaled(const uint8_t *vol, int64_t stride_slice, int64_t stride_row, int64_t stride_col,
+                               int n_slices, int h, int w, int dh, int dw, int hp, int wp, const int32_t *row_off,
+                               const int16_t *row_coef, const int32_t *col_off, const int16_t *col_coef, int area,
+                               float mean255, float inv_std255, float *out, void *stream);
+
 /* ---- D1 epilogue: fused BatchNorm(eval) + residual + ReLU on NHWC fp32 activations -----------------
  * replaces the elementwise tail of every conv block of the dense path:
  *          Bottleneck / BasicBlock forward         empanada/models/encoders/resnet.py:66-82,110-128
