@@ -601,16 +601,21 @@ extern "C" int emp_conv_k_slab_cin(int64_t M, int Cout, int batch, int has_resid
     return cg_plan(M, Cout, batch, has_residual != 0, true, true, Cin).slab;
 }
 
-// D4b (emp_conv1x1.hip): the weight-stationary kernel for short-K pointwise layers sums over 64-channel slabs
-extern "C" int emp_conv1x1_ws_eligible(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu);
-extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_launch(const float *x, const float *w, const float *scale, const float *shift,
+// D4b (emp_conv1x1.hip): the weight-stationary kernel for short-K pointwise layers.  Kind 1 (conv3 / shortcut shapes) sums
+// over 64-channel slabs; kind 2 (256 -> 64, 64 -> 64, 256 -> 128 without a residual) and the batched GEMM sum in the
+// order of the tiled kernel's plan, so emp_conv_k_slab* keep their answers for them.
+extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_kind(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu);
+extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_launch(int kind, const float *x, const float *w, const float *scale, const float *shift,
                                      const float *res, int64_t res_ps, int relu, int64_t M, int Cin, int Cout,
                                      float *out, int64_t out_ps, void *stream);
+extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_eligible(int batch, int64_t M, int N, int K, int slab);
+extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_launch(const float *A, const float *B, int batch, int64_t M, int N, int K, float *C,
+                                                                        void *stream);
 
 extern "C" int emp_conv_k_slab_geom(int64_t M, int Cout, int has_residual, int Cin, int KH, int KW, int stride, int pad,
                                     int relu)
 {
-    if (emp_conv1x1_ws_eligible(M, Cin, Cout, KH, KW, stride, pad, relu)) return 64;
+    if (emp_conv1x1_ws_kind(M, Cin, Cout, KH, KW, stride, pad, relu) == 1) return 64;
     return cg_plan(M, Cout, 1, has_residual != 0 && relu != 2, true, true, Cin).slab;
 }
 
@@ -644,10 +649,14 @@ extern "C" int emp_conv_bn_act_nhwc(const float *x, const float *w_okkc, const f
     const bool io_vec_ok = res_vec_ok && (out_pixel_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                            (!scale || (reinterpret_cast<uintptr_t>(scale) & 15) == 0) &&
                            (!shift || (reinterpret_cast<uintptr_t>(shift) & 15) == 0);
-    if (io_vec_ok && scale && shift && emp_conv1x1_ws_eligible(g.M, Cin, Cout, KH, KW, stride, pad, relu))
-        return emp_conv1x1_ws_launch(x, w_okkc, scale, shift, residual, res_pixel_stride, relu, g.M, Cin, Cout, out,
+    const int ws = io_vec_ok && scale && shift ? emp_conv1x1_ws_kind(g.M, Cin, Cout, KH, KW, stride, pad, relu) : 0;
+    if (ws == 1)
+        return emp_conv1x1_ws_launch(1, x, w_okkc, scale, shift, residual, res_pixel_stride, relu, g.M, Cin, Cout, out,
                                      out_pixel_stride, stream);
     const CgPlan pl = cg_plan(g.M, Cout, 1, residual != nullptr && relu != 2, res_vec_ok, true, Cin);
+    if (ws == 2 && !residual && pl.slab == 16)       // same summation order as the tiled kernel below
+        return emp_conv1x1_ws_launch(2, x, w_okkc, scale, shift, nullptr, res_pixel_stride, relu, g.M, Cin, Cout, out,
+                                     out_pixel_stride, stream);
     const bool narrow = pl.narrow, respf = pl.respf, bk16 = pl.slab == 16;
     EMP_REQUIRE((int64_t)pl.tiles_m * pl.tiles_n < (1LL << 28), "conv: too many tiles");
     g.tiles_m = pl.tiles_m;
@@ -948,6 +957,8 @@ extern "C" int emp_gemm_nt_batched(const float *A, const float *B, int batch, in
     g.M = M; g.out_ps = N; g.res_ps = N;
     g.x_bs = M * K; g.w_bs = (int64_t)N * K; g.out_bs = M * N; g.tiles = nullptr; g.proj_w = nullptr; g.proj_out = nullptr; g.proj_n = 0; g.hw = 1;
     const CgPlan pl = cg_plan(M, N, batch, false, true);
+    if ((reinterpret_cast<uintptr_t>(C) & 15) == 0 && emp_gemm_ws_eligible(batch, M, N, K, pl.slab))
+        return emp_gemm_ws_launch(A, B, batch, M, N, K, C, stream);       // short K: weight-stationary, same order
     const bool narrow = pl.narrow, bk16 = pl.slab == 16;
     g.tiles_m = pl.tiles_m;
     g.tiles_n = pl.tiles_n;

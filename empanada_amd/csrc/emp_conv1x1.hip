@@ -1,6 +1,6 @@
 // D4b: weight-stationary 1x1 convolution + BatchNorm (+ residual) (+ ReLU) for the SHORT-K pointwise layers of the
 // ResNet bottleneck (layer1 / layer2: conv3 64 -> 256 and 128 -> 512 with the identity added, the 64 -> 256 shortcut
-// projection).  gfx950 only.
+// projection; further shapes at the end of this comment).  gfx950 only.
 //
 // Why a second kernel.  These layers move 2.3-4.6 KB per pixel for 33-131 kFLOP: 14-28 flop per byte, at or below the
 // ridge of the fp32 matrix pipe (157 TF/s / 6.3 TB/s = 25).  The tiled implicit-GEMM kernel (emp_conv.hip) spends a
@@ -25,28 +25,56 @@
 // Summation order per output: one fmaf chain from +0 over 64-channel slabs ascending, inside a slab j = 0..31:
 // channel j, then channel 32 + j -- the order of emp_conv_bn_act_nhwc with a K-slab of 64 (emp_conv_k_slab_geom);
 // oracle/dense.py::conv_bn_act_nhwc(slab=64) reproduces it bit for bit.
+//
+// The same kernel, with the K-slab, the cout-group width and the pixels per wave step as template parameters, also takes
+// the short-K launches the tiled kernel is worst at (profiles/ws_shapes.md): the bottleneck's conv1 (256 -> 64, 64 -> 64,
+// 256 -> 128 with BatchNorm + ReLU) and the batched GEMM behind emp_gemm_nt_batched with K and N in {64, 128} (the
+// Winograd F(4x4,3x3) GEMMs of layer1 / layer2).  THOSE sum in the tiled kernel's own order -- slabs of S = 16 channels,
+// inside a slab c, c + S/2 for c = 0..S/2-1 -- so their results do not depend on which kernel ran.
 #include "emp_common.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define PW_THREADS 256
-#define PW_BN 128                  // couts per block
-#define PW_ROWS 32                 // pixels per wave tile
+#define PW_ROWS 32                 // pixels per 32 x 32 MFMA tile
+#define PW_MIN_ROWS 65536          // 64-slab shapes: fewest pixels worth the persistent grid
+#define PW_MIN_ROWS_PLAN 262144    // plan-order shapes and the batched GEMM: at least eight 32-row tiles per wave (256 CUs
+                                   // x 4 waves), so that the pipeline's fill and drain are a small part of a wave's life
 
 struct PwGeom {
     const float *x, *w, *scale, *shift, *res;
     float *out;
     int64_t M, out_ps, res_ps;
     int Cin, Cout, relu, groups, pix_blocks;
+    int batch;                     // GEMM form: entries per launch; x, w and out advance by x_bs, w_bs, out_bs per entry
+    int64_t x_bs, w_bs, out_bs;
 };
 
-template <int KS, bool RES, bool RELU>
+// KS:   Cin / 64.
+// S:    K-slab of the summation order: the k-step j of slab s consumes channels S s + j (lanes 0-31) and S s + S/2 + j
+//       (lanes 32-63), so lane (r, h) reads the S/2 contiguous channels [S s + h S/2, S s + h S/2 + S/2) of slab s --
+//       128 contiguous bytes at S = 64, 32-byte pieces of the same row at S = 16 -- and the weight fragments come from the
+//       matching LDS columns.  S = 64 for the conv3 / shortcut shapes, else the slab of the tiled kernel's plan
+//       (emp_conv_k_slab*), so that for those shapes the result does not depend on which kernel ran.
+// CT:   32-wide cout tiles of a block: 4 (128 couts, a lane holds 4 consecutive couts, float4 epilogue) or 2 (64 couts,
+//       a lane holds 2 consecutive couts; a half-wave store still covers a whole 256-byte pixel row).
+// PT:   32-pixel tiles per wave step (2 where the A registers allow it: more bytes in flight per wave for the layers
+//       with the fewest flops per byte).
+// GEMM: batched C_b = A_b B_b^T with the identity epilogue; a block takes a contiguous range of the launch's
+//       (entry, tile) sequence and re-stages the weights where the range crosses into the next entry.
+template <int KS, int S, int CT, int PT, bool GEMM, bool RES, bool RELU>
 __global__ __launch_bounds__(PW_THREADS, 1) void conv1x1_ws_kernel(PwGeom g)
 {
     constexpr int CIN = 64 * KS;
     constexpr int LD = CIN + 4;                        // LDS row (floats): 16 lanes x 16 B cover all 64 banks once
-    __shared__ __attribute__((aligned(16))) float Bs[PW_BN * LD];
+    constexpr int BN = 32 * CT;                        // couts per block
+    constexpr int NQ = CIN / 8;                        // float4 pieces of A per lane and pixel
+    constexpr int QS = S / 8;                          // of which per slab
+    constexpr int ROWS = PW_ROWS * PT;                 // pixels per wave step
+    static_assert(!RES || (CT == 4 && PT == 1 && !GEMM), "residual: 128-cout groups of the convolution form only");
+    static_assert(S == 16 || S == 32 || S == 64, "K-slab");
+    __shared__ __attribute__((aligned(16))) float Bs[BN * LD];
 
     // blockIdx -> (pixel block pb, cout group gi): consecutive hardware block ids go to different XCDs; the cout
     // groups of one pixel block take consecutive slots of ONE XCD
@@ -55,194 +83,295 @@ __global__ __launch_bounds__(PW_THREADS, 1) void conv1x1_ws_kernel(PwGeom g)
     const int per_xcd = g.pix_blocks >> 3;             // pixel blocks per XCD (pix_blocks is a multiple of 8)
     const int gi = slot % g.groups;
     const int pb = xcd * per_xcd + slot / g.groups;
-    const int n0 = gi * PW_BN;
+    const int n0 = GEMM ? 0 : gi * BN;
     const int tid = threadIdx.x;
+    const float *xb = g.x, *wb = g.w;                  // the current batch entry's operands (GEMM form: they move)
+    float *ob = g.out;
 
-    // weights of couts n0 + 4 c + j  ->  LDS row j * 32 + c
-    for (int idx = tid; idx < PW_BN * (CIN / 4); idx += PW_THREADS) {
-        const int rr = idx / (CIN / 4), k4 = idx - rr * (CIN / 4);
-        const int co = n0 + 4 * (rr & 31) + (rr >> 5);
-        *reinterpret_cast<float4 *>(&Bs[rr * LD + 4 * k4]) = *reinterpret_cast<const float4 *>(g.w + (int64_t)co * CIN + 4 * k4);
-    }
-    __syncthreads();
+    // weights of couts n0 + CT c + j  ->  LDS row j * 32 + c
+    auto stage = [&]() {
+        for (int idx = tid; idx < BN * (CIN / 4); idx += PW_THREADS) {
+            const int rr = idx / (CIN / 4), k4 = idx - rr * (CIN / 4);
+            const int cw = n0 + CT * (rr & 31) + (rr >> 5);
+            *reinterpret_cast<float4 *>(&Bs[rr * LD + 4 * k4]) = *reinterpret_cast<const float4 *>(wb + (int64_t)cw * CIN + 4 * k4);
+        }
+        __syncthreads();
+    };
 
     const int wave = tid >> 6, lane = tid & 63;
     const int r = lane & 31, hh = lane >> 5;
-    const int co = n0 + 4 * r;                         // the lane's four consecutive couts
-    float sc[4], sh[4];                                // scale and shift are both present (eligibility)
-    { const float4 t = *reinterpret_cast<const float4 *>(g.scale + co); sc[0] = t.x; sc[1] = t.y; sc[2] = t.z; sc[3] = t.w; }
-    { const float4 t = *reinterpret_cast<const float4 *>(g.shift + co); sh[0] = t.x; sh[1] = t.y; sh[2] = t.z; sh[3] = t.w; }
+    const int co = n0 + CT * r;                        // the lane's CT consecutive couts
+    float sc[CT], sh[CT];                              // scale and shift are both present (eligibility)
+    if constexpr (!GEMM) {
+        if constexpr (CT == 4) {
+            { const float4 t = *reinterpret_cast<const float4 *>(g.scale + co); sc[0] = t.x; sc[1] = t.y; sc[2] = t.z; sc[3] = t.w; }
+            { const float4 t = *reinterpret_cast<const float4 *>(g.shift + co); sh[0] = t.x; sh[1] = t.y; sh[2] = t.z; sh[3] = t.w; }
+        } else {
+            { const float2 t = *reinterpret_cast<const float2 *>(g.scale + co); sc[0] = t.x; sc[1] = t.y; }
+            { const float2 t = *reinterpret_cast<const float2 *>(g.shift + co); sh[0] = t.x; sh[1] = t.y; }
+        }
+    }
 
-    const int64_t n_tiles = (g.M + PW_ROWS - 1) / PW_ROWS;
-    const int64_t stride_t = (int64_t)g.pix_blocks * (PW_THREADS / 64);
-    const float *Bl = &Bs[r * LD + hh * 32];           // the lane's row of tile 0, its half of a slab
+    const int64_t n_tiles = (g.M + ROWS - 1) / ROWS;
+    const int64_t n_full = g.M / ROWS;
+    const float *Bl = &Bs[r * LD + hh * (S / 2)];      // the lane's row of tile 0, its half of a slab
+    const int64_t ops = GEMM ? (int64_t)BN : g.out_ps; // (GEMM form: C rows are dense, so the epilogue's row offsets are immediates)
 
     // ---- the pieces of a tile's life --------------------------------------------------------------------------
-    // A = 128 contiguous bytes per lane and slab
-    auto load_a = [&](int64_t t, float4 (&a)[KS][8]) {
-        const int64_t pa = t * PW_ROWS + r;            // (only full tiles come through here)
-        const float *ap = g.x + pa * CIN + hh * 32;
+    // A = S/2 contiguous channels per lane and slab; piece i of a lane is slab i / QS, float4 i % QS of its half
+    auto load_a = [&](int64_t t, float4 (&a)[PT][NQ]) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s)
+        for (int p = 0; p < PT; ++p) {
+            const int64_t pa = t * ROWS + PW_ROWS * p + r;     // (only full tiles come through here)
+            const float *ap = xb + pa * CIN + hh * (S / 2);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) a[s][q] = *reinterpret_cast<const float4 *>(ap + 64 * s + 4 * q);
+            for (int i = 0; i < NQ; ++i) a[p][i] = *reinterpret_cast<const float4 *>(ap + S * (i / QS) + 4 * (i % QS));
+        }
     };
     // residual of the lane's 16 (pixel, 4 couts) outputs
     auto load_rs = [&](int64_t t, float4 (&rs)[RES ? 16 : 1]) {
         if constexpr (RES) {
-            const float *rp = g.res + (t * PW_ROWS + 4 * hh) * g.res_ps + co;
+            const float *rp = g.res + (t * ROWS + 4 * hh) * g.res_ps + co;
 #pragma unroll
             for (int q = 0; q < 16; ++q)
                 rs[q] = *reinterpret_cast<const float4 *>(rp + (int64_t)((q & 3) + 8 * (q >> 2)) * g.res_ps);
         }
     };
-    auto mma = [&](f32x16 (&acc)[4], const float4 (&a)[KS][8]) {
+    auto mma = [&](f32x16 (&acc)[PT * CT], const float4 (&a)[PT][NQ]) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < PT * CT; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
-        // the weight fragments do not depend on the tile: without this the compiler hoists all 32 * KS float4 LDS reads
+        // the weight fragments do not depend on the tile: without this the compiler hoists all CT * NQ float4 LDS reads
         // of a lane out of the tile loop (512+ registers) -- the address is made opaque once per tile instead
         int opaque = 0;
         asm volatile("" : "+v"(opaque));               // (an offset, not the pointer: the LDS address space must survive)
         const float *Bt = Bl + opaque;
 #pragma unroll
-        for (int s = 0; s < KS; ++s)
+        for (int i = 0; i < NQ; ++i) {
+            float4 b[CT];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                float4 b[4];
+            for (int j = 0; j < CT; ++j) b[j] = *reinterpret_cast<const float4 *>(Bt + j * 32 * LD + S * (i / QS) + 4 * (i % QS));
 #pragma unroll
-                for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4 *>(Bt + j * 32 * LD + 64 * s + 4 * q);
+            for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float av = e == 0 ? a[s][q].x : e == 1 ? a[s][q].y : e == 2 ? a[s][q].z : a[s][q].w;
+                for (int p = 0; p < PT; ++p) {
+                    const float av = e == 0 ? a[p][i].x : e == 1 ? a[p][i].y : e == 2 ? a[p][i].z : a[p][i].w;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
+                    for (int j = 0; j < CT; ++j) {
                         const float bv = e == 0 ? b[j].x : e == 1 ? b[j].y : e == 2 ? b[j].z : b[j].w;
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[j], 0, 0, 0);
+                        acc[p * CT + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[p * CT + j], 0, 0, 0);
                     }
                 }
-            }
+        }
     };
-    // epilogue straight from the accumulators: register q of tile j = pixel row(q, hh), cout co + j
-    auto outv = [&](const f32x16 (&acc)[4], const float4 (&rs)[RES ? 16 : 1], int q) {
-        float v[4] = {acc[0][q], acc[1][q], acc[2][q], acc[3][q]};
+    // epilogue straight from the accumulators: register q of tile (p, j) = pixel row(q, hh) of pixel tile p, cout co + j
+    auto put = [&](float *dst, const f32x16 (&acc)[PT * CT], int p, const float4 (&rs)[RES ? 16 : 1], int q) {
+        float v[CT];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(__fmul_rn(v[e], sc[e]), sh[e]);
+        for (int e = 0; e < CT; ++e) v[e] = acc[p * CT + e][q];
+        if constexpr (!GEMM) {
+#pragma unroll
+            for (int e = 0; e < CT; ++e) v[e] = __fadd_rn(__fmul_rn(v[e], sc[e]), sh[e]);
+        }
         if constexpr (RES) {
             v[0] = __fadd_rn(v[0], rs[q].x); v[1] = __fadd_rn(v[1], rs[q].y);
             v[2] = __fadd_rn(v[2], rs[q].z); v[3] = __fadd_rn(v[3], rs[q].w);
         }
         if constexpr (RELU) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            for (int e = 0; e < CT; ++e) v[e] = fmaxf(v[e], 0.f);
         }
-        return make_float4(v[0], v[1], v[2], v[3]);
+        if constexpr (CT == 4) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        else *reinterpret_cast<float2 *>(dst) = make_float2(v[0], v[1]);
     };
-    auto epi = [&](const f32x16 (&acc)[4], const float4 (&rs)[RES ? 16 : 1], int64_t t) {       // full tiles
-        float *op = g.out + (t * PW_ROWS + 4 * hh) * g.out_ps + co;
+    auto epi = [&](const f32x16 (&acc)[PT * CT], const float4 (&rs)[RES ? 16 : 1], int64_t t) {       // full tiles
 #pragma unroll
-        for (int q = 0; q < 16; ++q)
-            *reinterpret_cast<float4 *>(op + (int64_t)((q & 3) + 8 * (q >> 2)) * g.out_ps) = outv(acc, rs, q);
+        for (int p = 0; p < PT; ++p) {
+            float *op = ob + (t * ROWS + PW_ROWS * p + 4 * hh) * ops + co;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) put(op + (int64_t)((q & 3) + 8 * (q >> 2)) * ops, acc, p, rs, q);
+        }
     };
 
-    // ---- full tiles, software-pipelined over two register sets: in phase i the residual of tile i and the activations
-    // of tile i + 1 are requested, then the MFMAs of tile i (into acc[i % 2]) and the epilogue of tile i - 1 (out of
-    // acc[(i - 1) % 2]) sit in ONE basic block, so that the scheduler can slot the epilogue's vector ALU work and
-    // stores between the matrix instructions -- with one wave per SIMD nothing else would fill the matrix pipe's
-    // shadow.  Loads are consumed one phase (128-256 MFMAs, 3-7 us) after they were issued.
-    const int64_t n_full = g.M / PW_ROWS;
-    const int64_t t_first = (int64_t)pb * (PW_THREADS / 64) + wave;
-    if (t_first < n_full) {
-        const int64_t m = (n_full - t_first + stride_t - 1) / stride_t;       // tiles of this wave
-        auto tile = [&](int64_t i) { return t_first + (i < m ? i : m - 1) * stride_t; };   // (past the end: re-request the last)
-        float4 a0[KS][8], a1[KS][8], rs0[RES ? 16 : 1], rs1[RES ? 16 : 1];
-        f32x16 acc0[4], acc1[4];
-        load_a(tile(0), a0);
-        load_rs(tile(0), rs0);
-        load_a(tile(1), a1);
-        mma(acc0, a0);
-        int64_t i = 1;
-        for (; i + 1 < m; i += 2) {
-            load_rs(tile(i), rs1);
-            load_a(tile(i + 1), a0);
-            mma(acc1, a1);
-            epi(acc0, rs0, tile(i - 1));
-            load_rs(tile(i + 1), rs0);
-            load_a(tile(i + 2), a1);
+    // the tiles t_first, t_first + stride_t, ... below t_end (<= n_tiles) of the current entry
+    auto run = [&](const int64_t t_first, const int64_t stride_t, const int64_t t_end) {
+        // ---- full tiles, software-pipelined over two register sets: in phase i the residual of tile i and the
+        // activations of tile i + 1 are requested, then the MFMAs of tile i (into acc[i % 2]) and the epilogue of tile
+        // i - 1 (out of acc[(i - 1) % 2]) sit in ONE basic block, so that the scheduler can slot the epilogue's vector ALU
+        // work and stores between the matrix instructions -- with one wave per SIMD nothing else would fill the matrix
+        // pipe's shadow.  Loads are consumed one phase (64-512 MFMAs, 2-14 us) after they were issued.
+        const int64_t f_end = n_full < t_end ? n_full : t_end;
+        if (t_first < f_end) {
+            const int64_t m = (f_end - t_first + stride_t - 1) / stride_t;        // tiles of this wave
+            auto tile = [&](int64_t i) { return t_first + (i < m ? i : m - 1) * stride_t; };   // (past the end: re-request the last)
+            float4 a0[PT][NQ], a1[PT][NQ], rs0[RES ? 16 : 1], rs1[RES ? 16 : 1];
+            f32x16 acc0[PT * CT], acc1[PT * CT];
+            load_a(tile(0), a0);
+            load_rs(tile(0), rs0);
+            load_a(tile(1), a1);
             mma(acc0, a0);
-            epi(acc1, rs1, tile(i));
-        }
-        if (i < m) {                                   // one more tile (odd index), then its epilogue
-            load_rs(tile(i), rs1);
-            mma(acc1, a1);
-            epi(acc0, rs0, tile(i - 1));
-            epi(acc1, rs1, tile(i));
-        } else {
-            epi(acc0, rs0, tile(i - 1));
-        }
-    }
-    // ---- the launch's one partial tile (M % 32 rows), by the wave whose turn it would be: clamped loads, masked stores
-    if (n_full < n_tiles && (n_full - t_first) % stride_t == 0 && n_full >= t_first) {
-        const int64_t p0 = n_full * PW_ROWS;
-        const int64_t pa = (p0 + r < g.M) ? p0 + r : g.M - 1;
-        const float *ap = g.x + pa * CIN + hh * 32;
-        float4 a[KS][8], rs[RES ? 16 : 1];
-        f32x16 acc[4];
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) a[s][q] = *reinterpret_cast<const float4 *>(ap + 64 * s + 4 * q);
-        if constexpr (RES) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                int64_t p = p0 + (q & 3) + 8 * (q >> 2) + 4 * hh;
-                p = p < g.M ? p : g.M - 1;
-                rs[q] = *reinterpret_cast<const float4 *>(g.res + p * g.res_ps + co);
+            int64_t i = 1;
+            for (; i + 1 < m; i += 2) {
+                load_rs(tile(i), rs1);
+                load_a(tile(i + 1), a0);
+                mma(acc1, a1);
+                epi(acc0, rs0, tile(i - 1));
+                load_rs(tile(i + 1), rs0);
+                load_a(tile(i + 2), a1);
+                mma(acc0, a0);
+                epi(acc1, rs1, tile(i));
+            }
+            if (i < m) {                               // one more tile (odd index), then its epilogue
+                load_rs(tile(i), rs1);
+                mma(acc1, a1);
+                epi(acc0, rs0, tile(i - 1));
+                epi(acc1, rs1, tile(i));
+            } else {
+                epi(acc0, rs0, tile(i - 1));
             }
         }
-        mma(acc, a);
+        // ---- the entry's one partial tile (M % ROWS rows), by the wave whose turn it would be: clamped loads, masked stores
+        if (n_full < t_end && n_full >= t_first && (n_full - t_first) % stride_t == 0) {
+            const int64_t p0 = n_full * ROWS;
+            float4 a[PT][NQ], rs[RES ? 16 : 1];
+            f32x16 acc[PT * CT];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int64_t p = p0 + (q & 3) + 8 * (q >> 2) + 4 * hh;
-            if (p < g.M) *reinterpret_cast<float4 *>(g.out + p * g.out_ps + co) = outv(acc, rs, q);
+            for (int p = 0; p < PT; ++p) {
+                const int64_t pr = p0 + PW_ROWS * p + r;
+                const float *ap = xb + (pr < g.M ? pr : g.M - 1) * CIN + hh * (S / 2);
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) a[p][i] = *reinterpret_cast<const float4 *>(ap + S * (i / QS) + 4 * (i % QS));
+            }
+            if constexpr (RES) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    int64_t p = p0 + (q & 3) + 8 * (q >> 2) + 4 * hh;
+                    p = p < g.M ? p : g.M - 1;
+                    rs[q] = *reinterpret_cast<const float4 *>(g.res + p * g.res_ps + co);
+                }
+            }
+            mma(acc, a);
+#pragma unroll
+            for (int p = 0; p < PT; ++p)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int64_t px = p0 + PW_ROWS * p + (q & 3) + 8 * (q >> 2) + 4 * hh;
+                    if (px < g.M) put(ob + px * ops + co, acc, p, rs, q);
+                }
         }
+    };
+
+    if constexpr (GEMM) {
+        // block k of n takes the tiles [G k / n, G (k + 1) / n) of the launch's G = batch x n_tiles (entry, tile) sequence,
+        // its four waves alternating inside the part that lies in one entry
+        const int64_t G = (int64_t)g.batch * n_tiles;
+        int64_t lo = G * bid / gridDim.x;
+        const int64_t hi = G * (bid + 1) / gridDim.x;
+        while (lo < hi) {
+            const int64_t b = lo / n_tiles, t0 = lo - b * n_tiles;
+            const int64_t t1 = hi - lo < n_tiles - t0 ? t0 + (hi - lo) : n_tiles;
+            xb = g.x + b * g.x_bs;
+            wb = g.w + b * g.w_bs;
+            ob = g.out + b * g.out_bs;
+            stage();
+            run(t0 + wave, PW_THREADS / 64, t1);
+            __syncthreads();                           // every wave is done with this entry's weights
+            lo += t1 - t0;
+        }
+    } else {
+        stage();
+        run((int64_t)pb * (PW_THREADS / 64) + wave, (int64_t)g.pix_blocks * (PW_THREADS / 64), n_tiles);
     }
 }
 
-// Shapes the weight-stationary kernel takes (everything else stays on conv_igemm_f32_kernel): 1x1, stride 1, no
-// padding, Cin 64 or 128, whole 128-cout groups, and enough pixels to give every CU's eight waves several tiles.
-// (the launcher additionally wants scale AND shift -- every call site on the path is conv + BatchNorm)
-extern "C" int emp_conv1x1_ws_eligible(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu)
+static bool pw_off()
 {
     static const char *off = getenv("EMP_CONV_NO_WS");         // experiments only (A/B against the tiled kernel)
-    if (off && off[0] == '1') return 0;
-    return KH == 1 && KW == 1 && stride == 1 && pad == 0 && (Cin == 64 || Cin == 128) && Cout % PW_BN == 0 &&
-           Cout / PW_BN <= 8 && relu != 2 && M >= 65536;
+    return off && off[0] == '1';
 }
 
-// called by emp_conv_bn_act_nhwc for eligible shapes (pointers and strides already checked for 16-byte alignment)
-extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_launch(const float *x, const float *w, const float *scale, const float *shift,
+// Shapes the weight-stationary kernel takes (everything else stays on conv_igemm_f32_kernel): 1x1, stride 1, no padding,
+// and enough pixels to give every CU's waves several tiles.
+//   1: Cin 64 or 128, whole 128-cout groups (conv3 + identity, the shortcut projection): K-slab 64;
+//   2: 256 -> 64, 64 -> 64, 256 -> 128 (the bottleneck's conv1 in layer1 / layer2): the K-slab of the tiled kernel's plan,
+//      which the caller passes to the launcher; without a residual only (emp_conv_bn_act_nhwc checks that, and that the
+//      plan's slab is 16 -- it always is at these sizes unless an experiment switch forces 32).
+// (the launcher additionally wants scale AND shift -- every call site on the path is conv + BatchNorm)
+extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_kind(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu)
+{
+    if (pw_off()) return 0;
+    if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0 && relu != 2)) return 0;
+    if ((Cin == 64 || Cin == 128) && Cout % 128 == 0 && Cout / 128 <= 8 && M >= PW_MIN_ROWS) return 1;
+    if (M >= PW_MIN_ROWS_PLAN && ((Cin == 256 && Cout == 64) || (Cin == 64 && Cout == 64) || (Cin == 256 && Cout == 128)))
+        return 2;
+    return 0;
+}
+
+extern "C" int emp_conv1x1_ws_eligible(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu)
+{
+    return emp_conv1x1_ws_kind(M, Cin, Cout, KH, KW, stride, pad, relu) != 0;
+}
+
+// the batched GEMM emp_gemm_nt_batched hands over: K and N 64 or 128, the plan's K-slab 16, batch x M rows enough
+extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_eligible(int batch, int64_t M, int N, int K, int slab)
+{
+    if (pw_off()) return 0;
+    return (K == 64 || K == 128) && (N == 64 || N == 128) && slab == 16 && M >= PW_ROWS && (int64_t)batch * M >= PW_MIN_ROWS_PLAN;
+}
+
+template <int KS, int S, int CT, int PT, bool GEMM, bool RES>
+static void pw_go(const PwGeom &g, int blocks, hipStream_t st)
+{
+    if (g.relu) {
+        if constexpr (!GEMM) hipLaunchKernelGGL((conv1x1_ws_kernel<KS, S, CT, PT, GEMM, RES, true>), dim3(blocks), dim3(PW_THREADS), 0, st, g);
+    } else {
+        hipLaunchKernelGGL((conv1x1_ws_kernel<KS, S, CT, PT, GEMM, RES, false>), dim3(blocks), dim3(PW_THREADS), 0, st, g);
+    }
+}
+
+// called by emp_conv_bn_act_nhwc for eligible shapes (pointers and strides already checked for 16-byte alignment);
+// kind as emp_conv1x1_ws_kind answered (2: no residual, K-slab 16)
+extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_launch(int kind, const float *x, const float *w, const float *scale, const float *shift,
                                      const float *res, int64_t res_ps, int relu, int64_t M, int Cin, int Cout,
                                      float *out, int64_t out_ps, void *stream)
 {
     PwGeom g;
     g.x = x; g.w = w; g.scale = scale; g.shift = shift; g.res = res; g.out = out;
     g.M = M; g.out_ps = out_ps; g.res_ps = res_ps; g.Cin = Cin; g.Cout = Cout; g.relu = relu;
-    g.groups = Cout / PW_BN;
+    g.batch = 1; g.x_bs = g.w_bs = g.out_bs = 0;
+    g.groups = kind == 1 ? Cout / 128 : 1;
     // one block per CU (256 CUs): pix_blocks x groups blocks, pix_blocks a multiple of 8 (XCDs)
     int pix = 256 / g.groups;
     pix = pix / 8 * 8;
     if (pix < 8) pix = 8;
     g.pix_blocks = pix;
-    const dim3 grid(pix * g.groups), block(PW_THREADS);
+    const int blocks = pix * g.groups;
     hipStream_t st = emp_stream(stream);
-#define PW_GO(KS_, RES_, RELU_) hipLaunchKernelGGL((conv1x1_ws_kernel<KS_, RES_, RELU_>), grid, block, 0, st, g)
-#define PW_GO2(KS_, RES_) do { if (relu) PW_GO(KS_, RES_, true); else PW_GO(KS_, RES_, false); } while (0)
-    if (Cin == 64) { if (res) PW_GO2(1, true); else PW_GO2(1, false); }
-    else { if (res) PW_GO2(2, true); else PW_GO2(2, false); }
-#undef PW_GO2
-#undef PW_GO
+    if (kind == 1) {
+        if (Cin == 64) { if (res) pw_go<1, 64, 4, 1, false, true>(g, blocks, st); else pw_go<1, 64, 4, 1, false, false>(g, blocks, st); }
+        else { if (res) pw_go<2, 64, 4, 1, false, true>(g, blocks, st); else pw_go<2, 64, 4, 1, false, false>(g, blocks, st); }
+    } else {
+        if (Cin == 64) pw_go<1, 16, 2, 2, false, false>(g, blocks, st);           // 64 -> 64
+        else if (Cout == 64) pw_go<4, 16, 2, 1, false, false>(g, blocks, st);     // 256 -> 64
+        else pw_go<4, 16, 4, 1, false, false>(g, blocks, st);                     // 256 -> 128
+    }
     EMP_CHECK_LAUNCH("emp_conv_bn_act_nhwc(1x1 weight-stationary)");
+    return EMP_OK;
+}
+
+// called by emp_gemm_nt_batched for eligible shapes (A, B, C 16-byte aligned)
+extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_launch(const float *A, const float *B, int batch, int64_t M, int N, int K, float *C,
+                                                                        void *stream)
+{
+    PwGeom g;
+    g.x = A; g.w = B; g.scale = g.shift = g.res = nullptr; g.out = C;
+    g.M = M; g.out_ps = N; g.res_ps = N; g.Cin = K; g.Cout = N; g.relu = 0;
+    g.batch = batch; g.x_bs = M * K; g.w_bs = (int64_t)N * K; g.out_bs = M * N;
+    g.groups = 1; g.pix_blocks = 256;
+    hipStream_t st = emp_stream(stream);
+    if (K == 64) { if (N == 64) pw_go<1, 16, 2, 2, true, false>(g, 256, st); else pw_go<1, 16, 4, 1, true, false>(g, 256, st); }
+    else { if (N == 64) pw_go<2, 16, 2, 2, true, false>(g, 256, st); else pw_go<2, 16, 4, 1, true, false>(g, 256, st); }
+    EMP_CHECK_LAUNCH("emp_gemm_nt_batched(weight-stationary)");
     return EMP_OK;
 }

@@ -135,7 +135,13 @@ int emp_conv_k_slab_cin(int64_t M, int Cout, int batch, int has_residual, int Ci
  * (emp_conv1x1.hip: weights resident in LDS, activations straight into the MFMA operands, epilogue from the
  * accumulators).  Its summation order is the D4 order with a K-slab of 64: slabs of 64 channels ascending, inside a
  * slab j = 0..31: channel j, then channel 32 + j.  emp_conv_k_slab_geom returns the slab emp_conv_bn_act_nhwc will use
- * for a given geometry (64 for these layers, else emp_conv_k_slab_cin's answer); relu as in emp_conv_bn_act_nhwc. */
+ * for a given geometry (64 for these layers, else emp_conv_k_slab_cin's answer); relu as in emp_conv_bn_act_nhwc.
+ * The same kernel also takes, from 262 144 output pixels on and without a residual, the bottleneck's conv1 shapes
+ * 256 -> 64, 64 -> 64 and 256 -> 128, and inside emp_gemm_nt_batched the GEMMs with K and N in {64, 128} and
+ * batch * M >= 262 144 (the Winograd F(4x4,3x3) GEMMs of layer1 / layer2).  For THESE it sums in the order of the tiled
+ * kernel (K-slab emp_conv_k_slab_cin / emp_conv_k_slab, 16 at such sizes), so the result does not depend on which
+ * kernel ran and emp_conv_k_slab* answer as before.  emp_conv1x1_ws_eligible: 1 for every convolution geometry the
+ * kernel takes (for the conv1 shapes: given no residual); EMP_CONV_NO_WS=1 in the environment turns all of it off. */
 int emp_conv_k_slab_geom(int64_t M, int Cout, int has_residual, int Cin, int KH, int KW, int stride, int pad, int relu);
 int emp_conv1x1_ws_eligible(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu);
 /* relu == 2 selects the squeeze-excite gate epilogue (SqueezeExcite.forward, empanada/models/blocks.py:35-50:
