@@ -51,6 +51,8 @@ SIGNATURES = {
     'emp_gemm_nt_batched': (_I, [_P, _P, _I, _L, _I, _I, _P, _P]),
     'emp_wino4_input_transform': (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     'emp_wino4_output_transform': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P]),
+    'emp_wino4_conv_bn_act_nhwc': (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P, _P, _I, _P, _L, _P]),
+    'emp_wino4_fused_eligible': (_I, [_L, _I, _I, _I]),
     'emp_wino3_input_transform': (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _P]),
     'emp_wino3_output_transform': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P]),
     'emp_wino_gemm_fused': (_I, [_P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P, _P]),
@@ -186,19 +188,21 @@ def trace(msg):
         _TRACE.write('# ' + msg + '\n')
 
 
-def call(name, *args, alg_bytes=None, alg_flops=None):
-    """Call an int-returning ABI function; raise HipError with emp_last_error() on failure."""
+def call(name, *args, alg_bytes=None, alg_flops=None, profile_as=None):
+    """Call an int-returning ABI function; raise HipError with emp_last_error() on failure.  profile_as: the name the
+    call is accounted under in PROFILE / PROFILE_SKIP (a kernel that replaces calls of that name)."""
     lib = load()
+    pname = profile_as or name
     if _TRACE is not None:
         _TRACE.write(name + ' ' + ' '.join(str(a) for a in args if isinstance(a, (int, float)) and abs(a) < (1 << 40))
                      + '\n')
-    if PROFILE is not None and name not in PROFILE_SKIP:
+    if PROFILE is not None and pname not in PROFILE_SKIP:
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
         rc = getattr(lib, name)(*args)
         e1.record()
-        PROFILE.setdefault(name, []).append((e0, e1, alg_bytes, alg_flops))
+        PROFILE.setdefault(pname, []).append((e0, e1, alg_bytes, alg_flops))
     else:
         rc = getattr(lib, name)(*args)
     if rc != 0:
@@ -952,22 +956,37 @@ def wino4_filter_transform(w_oihw):
     return torch.stack(U, dim=0).float().contiguous()
 
 
-def wino4_conv_bn_act(x, U, tiles_dev, dil, scale=None, shift=None, relu=False, out=None):
-    """3x3 stride-1 convolution with padding == dilation through Winograd F(4x4,3x3) (emp_wino4_input_transform,
-    emp_gemm_nt_batched x 36, emp_wino4_output_transform); tiles from wino_tiles(..., m=4)."""
+def wino4_fused_eligible(T, Cin, Cout, has_scale_shift=True):
+    """True where wino4_conv_bn_act(fused=None) takes the one-kernel path (emp_wino4_fused_eligible)."""
+    return bool(load().emp_wino4_fused_eligible(int(T), int(Cin), int(Cout), int(bool(has_scale_shift))))
+
+
+def wino4_conv_bn_act(x, U, tiles_dev, dil, scale=None, shift=None, relu=False, out=None, fused=None):
+    """3x3 stride-1 convolution with padding == dilation through Winograd F(4x4,3x3); tiles from wino_tiles(..., m=4).
+    Three calls (emp_wino4_input_transform, emp_gemm_nt_batched x 36, emp_wino4_output_transform) or, for the short-K
+    sites, one (emp_wino4_conv_bn_act_nhwc: V and Mw never exist in memory; the same bits).  fused: None asks
+    emp_wino4_fused_eligible, False forces the three calls, True forces the one kernel (it raises for a shape the kernel
+    does not take; only the minimum size is waived)."""
     require_gpu()
     N, Cin, H, W = x.shape
     Cout = U.shape[1]
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
     T = tiles_dev.shape[0]
-    V = torch.empty((36, T, Cin), dtype=torch.float32, device=x.device)
-    Mw = torch.empty((36, T, Cout), dtype=torch.float32, device=x.device)
+    if fused is None:
+        fused = wino4_fused_eligible(T, Cin, Cout, scale is not None and shift is not None)
     if out is None:
         out = torch.empty((N, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     assert out.shape == (N, Cout, H, W) and out.stride(1) == 1
     ops = out.stride(3)
     assert out.stride(2) == W * ops and out.stride(0) == H * W * ops, "NHWC channel slice required"
     st = stream()
+    if fused:
+        call('emp_wino4_conv_bn_act_nhwc', x.data_ptr(), N, H, W, Cin, dil, _ptr(tiles_dev), T, _ptr(U), Cout,
+             _ptr(scale), _ptr(shift), int(bool(relu)), out.data_ptr(), ops, st, profile_as='emp_gemm_nt_batched',
+             alg_bytes=4 * (x.numel() + U.numel() + N * Cout * H * W), alg_flops=2 * 36 * T * Cout * Cin)
+        return out
+    V = torch.empty((36, T, Cin), dtype=torch.float32, device=x.device)
+    Mw = torch.empty((36, T, Cout), dtype=torch.float32, device=x.device)
     call('emp_wino4_input_transform', x.data_ptr(), N, H, W, Cin, dil, _ptr(tiles_dev), T, _ptr(V), st,
          alg_bytes=4 * (x.numel() + V.numel()))
     call('emp_gemm_nt_batched', _ptr(V), _ptr(U), 36, T, Cout, Cin, _ptr(Mw), st,

@@ -19,6 +19,7 @@
 //   (its own L2) works on a contiguous range of tiles, cout-tiles fastest, and the A slabs shared by the cout
 //   tiles of one pixel tile are fetched once per XCD.
 #include "emp_common.h"
+#include "emp_wino4.h"
 #include <stdlib.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1028,36 +1029,8 @@ extern "C" int emp_wino_output_transform(const float *Mw, const int32_t *tiles, 
 // now covers 4x4 outputs of its sub-grid and reads a 6x6 patch).  The transforms amplify rounding by about 10x
 // relative to the direct form (measured 1.3e-6 * sum|x||w| at K = 18432), so this variant is tested against a
 // looser stated tolerance and offered to the tuner only as an alternative.
-// B^T (Lavin & Gray), evaluated as:  r0 = (4 d0 - 5 d2) + d4;  r1 = (d3 + d4) - 4 (d1 + d2);
-//   r2 = (d4 - d3) + 4 (d1 - d2);  r3 = (d4 - d2) + 2 (d3 - d1);  r4 = (d4 - d2) + 2 (d1 - d3);  r5 = (4 d1 - 5 d3) + d5
-// A^T:  s0 = ((m0 + m1) + m2) + (m3 + m4);  s1 = (m1 - m2) + 2 (m3 - m4);  s2 = (m1 + m2) + 4 (m3 + m4);
-//   s3 = ((m1 - m2) + 8 (m3 - m4)) + m5         (every operation one fp32 rounding, columns first, then rows)
-struct v4 {
-    float x, y, z, w;
-};
-__device__ __forceinline__ v4 operator+(v4 a, v4 b) { return {__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w)}; }
-__device__ __forceinline__ v4 operator-(v4 a, v4 b) { return {__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z), __fsub_rn(a.w, b.w)}; }
-__device__ __forceinline__ v4 operator*(float k, v4 a) { return {__fmul_rn(k, a.x), __fmul_rn(k, a.y), __fmul_rn(k, a.z), __fmul_rn(k, a.w)}; }
-__device__ __forceinline__ v4 ldv4(const float4 *p) { float4 t = *p; return {t.x, t.y, t.z, t.w}; }
-__device__ __forceinline__ void stv4(float4 *p, v4 a) { *p = make_float4(a.x, a.y, a.z, a.w); }
-
-__device__ __forceinline__ void wino4_bt(const v4 d[6], v4 r[6])
-{
-    r[0] = (4.f * d[0] - 5.f * d[2]) + d[4];
-    r[1] = (d[3] + d[4]) - 4.f * (d[1] + d[2]);
-    r[2] = (d[4] - d[3]) + 4.f * (d[1] - d[2]);
-    r[3] = (d[4] - d[2]) + 2.f * (d[3] - d[1]);
-    r[4] = (d[4] - d[2]) + 2.f * (d[1] - d[3]);
-    r[5] = (4.f * d[1] - 5.f * d[3]) + d[5];
-}
-
-__device__ __forceinline__ void wino4_at(const v4 m[6], v4 s[4])
-{
-    s[0] = ((m[0] + m[1]) + m[2]) + (m[3] + m[4]);
-    s[1] = (m[1] - m[2]) + 2.f * (m[3] - m[4]);
-    s[2] = (m[1] + m[2]) + 4.f * (m[3] + m[4]);
-    s[3] = ((m[1] - m[2]) + 8.f * (m[3] - m[4])) + m[5];
-}
+// The transforms themselves (B^T, A^T, one fp32 rounding per operation, columns first, then rows) and the v4 helpers
+// are in emp_wino4.h, shared with the one-kernel path (emp_wino4.hip, D5d).
 
 // x (N,H,W,C) -> V (36, T, C); one thread per (tile, 4 channels)
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float *__restrict__ x, const int32_t *__restrict__ tiles,

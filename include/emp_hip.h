@@ -242,6 +242,18 @@ int emp_wino4_input_transform(const float *x, int N, int H, int W, int C, int di
 int emp_wino4_output_transform(const float *Mw, const int32_t *tiles, int64_t T, int N, int H, int W,
                                int Cout, int dil, const float *scale, const float *shift, int relu,
                                float *out, int64_t out_pixel_stride, void *stream);
+/* D5d: the three steps in ONE launch for 64 -> 64 and 128 -> 128 (emp_wino4.hip): V is kept in LDS one 16-channel slab
+ * at a time, M in the accumulators; nothing of V or Mw touches memory, no allocation, no sync.  Same tile table, U and
+ * output contract as above; scale AND shift required.  Per M value one fma chain from +0 over 16-channel slabs
+ * ascending, inside a slab c, c + 8 for c = 0..7 (a v_mfma_f32_16x16x4_f32 per step j with channels 2j, 2j + 8, 2j + 1,
+ * 2j + 9 on k = 0..3): the order of emp_gemm_nt_batched at K-slab 16, so the bits are those of the three calls wherever
+ * emp_conv_k_slab(T, Cout, 36, 0) == 16, which the launcher requires (with 16 T Cin < 2^30).
+ * emp_wino4_fused_eligible: 1 = _hip.wino4_conv_bn_act takes this kernel (an enabled width pair, both scale and shift,
+ * the K-slab 16 plan, at least the measured minimum of tiles; EMP_WINO4_NO_FUSED=1 in the environment turns it off).   */
+int emp_wino4_conv_bn_act_nhwc(const float *x, int N, int H, int W, int Cin, int dil, const int32_t *tiles, int64_t T,
+                               const float *U, int Cout, const float *scale, const float *shift, int relu,
+                               float *out, int64_t out_pixel_stride, void *stream);
+int emp_wino4_fused_eligible(int64_t T, int Cin, int Cout, int has_scale_shift);   /* 1 = wino4_conv_bn_act takes the fused kernel */
 
 /* ---- D5c: Winograd F(3x3, 3x3) (points 0, 1, -1, 2, inf): 5x5 patches, 25 positions, 3x3 outputs per tile -----
  * tiles as in D5 with outputs (y + d + a*d, x + d + b*d), a, b in 0..2.  Transforms: r[u] = left fold, over the
