@@ -65,6 +65,7 @@ SIGNATURES = {
     'emp_bn_relu_maxpool_nhwc': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     'emp_stem_conv7_bn_relu_maxpool': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     'emp_logits_to_prob': (_I, [_P, _I, _I, _L, _P, _P]),
+    'emp_upsample_bilinear_prob': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P]),
     'emp_pr_upsample2x': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'emp_pr_topk_work_bytes': (_L, [_I, _L]),
     'emp_pr_topk': (_I, [_P, _I, _L, _I, _P, _L, _P, _P]),
@@ -637,6 +638,26 @@ def upsample_bilinear(x, size, out=None):
     xs = (ctypes.c_int64 * 4)(*x.stride())
     ys = (ctypes.c_int64 * 4)(*out.stride())
     call('emp_upsample_bilinear', x.data_ptr(), N, C, h, w, xs, out.data_ptr(), H, W, ys, stream(),
+         alg_bytes=4 * (x.numel() + N * C * H * W))
+    return out
+
+
+def upsample_bilinear_prob(x, size, out=None, prob=True):
+    """upsample_bilinear(x, size) and, with prob, logits_to_prob of it (sigmoid for C == 1, softmax over dim 1 otherwise,
+    C <= 64) in one launch, bit-identical to the two calls; the full-resolution logits are never written.  `out` may be any
+    (N,C,H,W) fp32 view, e.g. slices [s, e) of a plane's head buffer; default: a new contiguous tensor
+    (emp_upsample_bilinear_prob)."""
+    require_gpu()
+    import ctypes
+    N, C, h, w = x.shape
+    H, W = int(size[0]), int(size[1])
+    assert x.is_cuda and x.dtype == torch.float32
+    if out is None:
+        out = torch.empty((N, C, H, W), dtype=torch.float32, device=x.device)
+    assert out.shape == (N, C, H, W) and out.dtype == torch.float32 and out.is_cuda
+    xs = (ctypes.c_int64 * 4)(*x.stride())
+    ys = (ctypes.c_int64 * 4)(*out.stride())
+    call('emp_upsample_bilinear_prob', x.data_ptr(), N, C, h, w, xs, out.data_ptr(), H, W, ys, int(bool(prob)), stream(),
          alg_bytes=4 * (x.numel() + N * C * H * W))
     return out
 

@@ -581,6 +581,9 @@ extern "C" int emp_bn_relu_maxpool_nhwc(const float *x, const float *scale, cons
 // (N, C, HW) fp32.  One streaming pass; every lane owns 4 consecutive pixels (float4 per channel plane).
 // y may be x itself (in place): no __restrict__ here -- a lane reads every channel of its pixels in the first two
 // loops and, in the third, each channel again right before it stores that same address.
+__device__ __forceinline__ float l2p_sigmoid(float v) { return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-v))); }
+__device__ __forceinline__ float l2p_exp(float v, float m) { return expf(__fsub_rn(v, m)); }
+
 template <int VEC>
 __global__ __launch_bounds__(256) void logits_to_prob_kernel(const float *x, int C, int64_t HW, int64_t total, float *y)
 {
@@ -595,7 +598,7 @@ __global__ __launch_bounds__(256) void logits_to_prob_kernel(const float *x, int
             if constexpr (VEC == 4) { const float4 t = *reinterpret_cast<const float4 *>(xp); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
             else v[0] = xp[0];
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = __fdiv_rn(1.f, __fadd_rn(1.f, expf(-v[e])));
+            for (int e = 0; e < VEC; ++e) v[e] = l2p_sigmoid(v[e]);
             if constexpr (VEC == 4) *reinterpret_cast<float4 *>(yp) = make_float4(v[0], v[1], v[2], v[3]);
             else yp[0] = v[0];
         } else {
@@ -607,10 +610,10 @@ __global__ __launch_bounds__(256) void logits_to_prob_kernel(const float *x, int
                 for (int e = 0; e < VEC; ++e) m[e] = fmaxf(m[e], xp[c * HW + e]);
             for (int c = 0; c < C; ++c)
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) sum[e] = __fadd_rn(sum[e], expf(__fsub_rn(xp[c * HW + e], m[e])));
+                for (int e = 0; e < VEC; ++e) sum[e] = __fadd_rn(sum[e], l2p_exp(xp[c * HW + e], m[e]));
             for (int c = 0; c < C; ++c)
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) yp[c * HW + e] = __fdiv_rn(expf(__fsub_rn(xp[c * HW + e], m[e])), sum[e]);
+                for (int e = 0; e < VEC; ++e) yp[c * HW + e] = __fdiv_rn(l2p_exp(xp[c * HW + e], m[e]), sum[e]);
         }
     }
 }
@@ -644,7 +647,7 @@ __global__ __launch_bounds__(256) void softmax4_kernel(const float *x, int C, in
             if (c < C)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[c][e] = expf(__fsub_rn(v[c][e], m[e]));
+                    v[c][e] = l2p_exp(v[c][e], m[e]);
                     sum[e] = __fadd_rn(sum[e], v[c][e]);
                 }
 #pragma unroll
@@ -676,5 +679,139 @@ extern "C" int emp_logits_to_prob(const float *logits, int N, int C, int64_t HW,
                            logits, C, HW, total, prob);
     }
     EMP_CHECK_LAUNCH("emp_logits_to_prob");
+    return EMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// D3 + D2 in one launch: the last x4 up-sampling of a head fused with logits_to_prob, so that a full-resolution head is
+// written once, where the post-processing reads it (a slice view of a plane buffer: y goes through strides like D3).
+// A lane owns 4 consecutive output columns of one (n, Y) row and ALL channels of those pixels: the source coordinates are
+// worked out once per pixel, the up-sampled logits of up to L2P_CMAX channels stay in registers (more channels: the
+// bilinear mix is evaluated again in each of the three softmax passes -- the same operations, so the same bits).
+// up_src / up_mix and l2p_sigmoid / l2p_exp are the device functions of D3 and D2: the result is bit-identical to
+// emp_upsample_bilinear followed by emp_logits_to_prob.
+struct UpTap {
+    int64_t o00, o01, o10, o11;                                     // element offsets of the four source texels (channel 0)
+    float lx, ly;
+};
+
+__device__ __forceinline__ float up_tap(const float *__restrict__ xc, const UpTap &t)
+{
+    return up_mix(xc[t.o00], xc[t.o01], xc[t.o10], xc[t.o11], t.lx, t.ly);
+}
+
+__device__ __forceinline__ void up_store4(float *out, int X0, int W, int64_t ys_w, const float (&o)[4])
+{
+    if (ys_w == 1 && X0 + 3 < W && ((reinterpret_cast<uintptr_t>(out + X0) & 15) == 0)) {
+        *reinterpret_cast<float4 *>(out + X0) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (X0 + j < W) out[(X0 + j) * ys_w] = o[j];
+    }
+}
+
+// MODE 0: one channel (sigmoid); 1: 2..L2P_CMAX channels, logits in registers; 2: up to 64 channels, three passes
+template <int MODE>
+__global__ __launch_bounds__(256) void upsample_prob_kernel(const float *__restrict__ x, float *__restrict__ y, UpGeom g)
+{
+    const int W4 = (g.W + 3) >> 2;
+    const int64_t total = (int64_t)g.N * g.H * W4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int X0 = (int)(i % W4) * 4;
+        const int64_t p = i / W4;
+        const int Y = (int)(p % g.H);
+        const int n = (int)(p / g.H);
+        int y0, y1;
+        float ly;
+        up_src(g.ry, Y, g.h, y0, y1, ly);
+        const float *xn = x + n * g.xs_n;
+        float *out = y + n * g.ys_n + Y * g.ys_h;
+        UpTap t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int X = min(X0 + j, g.W - 1);                     // columns past W are computed in range, never stored
+            int x0, x1;
+            float lx;
+            up_src(g.rx, X, g.w, x0, x1, lx);
+            t[j].o00 = y0 * g.xs_h + x0 * g.xs_w;
+            t[j].o01 = y0 * g.xs_h + x1 * g.xs_w;
+            t[j].o10 = y1 * g.xs_h + x0 * g.xs_w;
+            t[j].o11 = y1 * g.xs_h + x1 * g.xs_w;
+            t[j].lx = lx;
+            t[j].ly = ly;
+        }
+        if constexpr (MODE == 0) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = l2p_sigmoid(up_tap(xn, t[j]));
+            up_store4(out, X0, g.W, g.ys_w, o);
+        } else if constexpr (MODE == 1) {
+            float v[L2P_CMAX][4];
+            float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < L2P_CMAX; ++c)
+                if (c < g.C)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        v[c][j] = up_tap(xn + c * g.xs_c, t[j]);
+                        m[j] = fmaxf(m[j], v[c][j]);
+                    }
+#pragma unroll
+            for (int c = 0; c < L2P_CMAX; ++c)
+                if (c < g.C)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        v[c][j] = l2p_exp(v[c][j], m[j]);
+                        sum[j] = __fadd_rn(sum[j], v[c][j]);
+                    }
+#pragma unroll
+            for (int c = 0; c < L2P_CMAX; ++c)
+                if (c < g.C) {
+                    float o[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[j] = __fdiv_rn(v[c][j], sum[j]);
+                    up_store4(out + c * g.ys_c, X0, g.W, g.ys_w, o);
+                }
+        } else {
+            float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, sum[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int c = 0; c < g.C; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], up_tap(xn + c * g.xs_c, t[j]));
+            for (int c = 0; c < g.C; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum[j] = __fadd_rn(sum[j], l2p_exp(up_tap(xn + c * g.xs_c, t[j]), m[j]));
+            for (int c = 0; c < g.C; ++c) {
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = __fdiv_rn(l2p_exp(up_tap(xn + c * g.xs_c, t[j]), m[j]), sum[j]);
+                up_store4(out + c * g.ys_c, X0, g.W, g.ys_w, o);
+            }
+        }
+    }
+}
+
+extern "C" int emp_upsample_bilinear_prob(const float *x, int N, int C, int h, int w, const int64_t *x_strides,
+                                          float *y, int H, int W, const int64_t *y_strides, int prob, void *stream)
+{
+    EMP_REQUIRE(x && y && x_strides && y_strides, "upsample_prob: null pointer");
+    EMP_REQUIRE(N >= 0 && C > 0 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_prob: bad shape");
+    EMP_REQUIRE(h < (1 << 24) && w < (1 << 24) && H < (1 << 24) && W < (1 << 24), "upsample_prob: sizes exceed fp32 integers");
+    EMP_REQUIRE(prob == 0 || prob == 1, "upsample_prob: prob must be 0 or 1");
+    if (prob == 0) return emp_upsample_bilinear(x, N, C, h, w, x_strides, y, H, W, y_strides, stream);
+    EMP_REQUIRE(C <= 64, "upsample_prob: more than 64 channels");
+    if (N == 0) return EMP_OK;
+    UpGeom g;
+    g.N = N; g.C = C; g.h = h; g.w = w; g.H = H; g.W = W;
+    g.xs_n = x_strides[0]; g.xs_c = x_strides[1]; g.xs_h = x_strides[2]; g.xs_w = x_strides[3];
+    g.ys_n = y_strides[0]; g.ys_c = y_strides[1]; g.ys_h = y_strides[2]; g.ys_w = y_strides[3];
+    g.ry = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+    g.rx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    const int64_t total = (int64_t)N * H * ((W + 3) / 4);
+    const dim3 grid(emp_grid(total, 256, 16384));
+    if (C == 1) hipLaunchKernelGGL(upsample_prob_kernel<0>, grid, dim3(256), 0, emp_stream(stream), x, y, g);
+    else if (C <= L2P_CMAX) hipLaunchKernelGGL(upsample_prob_kernel<1>, grid, dim3(256), 0, emp_stream(stream), x, y, g);
+    else hipLaunchKernelGGL(upsample_prob_kernel<2>, grid, dim3(256), 0, emp_stream(stream), x, y, g);
+    EMP_CHECK_LAUNCH("emp_upsample_bilinear_prob");
     return EMP_OK;
 }

@@ -10,7 +10,10 @@ class -- as ONE call that keeps the volume, the head tensors of a plane and ever
 With torch.distributed initialised (one process per GPU, backend 'nccl') every rank calls it with the same volume: the
 slices of every plane are split into contiguous blocks over the ranks and each rank writes its own z-slab
 (empanada_amd/inference/sharded.py).  Results are identical to the per-slice protocol on the same head tensors
-(tests/test_pipeline_gpu.py); bench.py times the same sequence with planted heads.
+(tests/test_pipeline_gpu.py).  bench.py times a pipeline of its own on planted heads (tuned sites, graph replay, two
+streams); the product's form of that is `pipeline=VolumePipeline(engine)` (empanada_amd/inference/pipeline.py), which
+computes the same volumes as the plain call (tests/test_volume_pipeline_gpu.py) and is timed by
+tools/bench_infer_volume.py.
 """
 import numpy as np
 import torch
@@ -48,7 +51,7 @@ def _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps):
 
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
-                 out=None, batch_pixels=32 * 1024 * 1024, render_steps=2, group=None, downsample_f=1):
+                 out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -59,6 +62,10 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     in-plane by f before the model sees it (DeviceVolume(scale=f)), the semantic head is rendered with log2 f more
     PointRend steps, the instance cells are enlarged by f more, and the labels come out at the full (D, H, W).  Needs
     a Render engine; a DeviceVolume passed in must have been built with scale=f.
+    pipeline: a VolumePipeline built for this engine (inference/pipeline.py): the same result through tuned call sites,
+    graph replay, heads written in place and two streams; its own batch_pixels sizes the model calls (passing another
+    value here as well is an error).  The result gains 'pipeline': what ran.
+    batch_pixels: output pixels per model call; None = 32 Mi pixels, or the pipeline's value with pipeline=.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -74,6 +81,10 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         raise ValueError("downsample_f > 1 needs a Render engine (PanopticDeepLabRenderEngine3d: model(x, render_steps, "
                          "interpolate_ins) and `upsampling`); the plain engines cannot render the labels back to full "
                          f"resolution, got {type(engine).__name__}")
+    if pipeline is not None:
+        pipeline.check(engine, axes, batch_pixels)
+    elif batch_pixels is None:
+        batch_pixels = 32 * 1024 * 1024
     if isinstance(volume, DeviceVolume):
         dv = volume
         if dv.scale != f:
@@ -87,28 +98,37 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                   confidence_thr=engine.confidence_thr, median_kernel_size=getattr(engine, 'ks', 1),
                   coarse_boundaries=bool(getattr(engine, 'coarse_boundaries', False)),
                   max_centers=getattr(engine, 'max_centers', None), upsampling=f)
+    if len(axes) == 1:
+        assert axes[0] == 'xy', "stack mode runs along z (axes=('xy',))"
+
+    def track(pan, axis, base):
+        h, w = dv.plane_shape(axis)
+        return sharded.track_plane(pan[:, :h, :w].contiguous(), axis, shape3d, labels, thing_list, div, merge_iou_thr,
+                                   merge_ioa_thr, inst_base=base, group=group)
+
+    def finish(planes):
+        if len(axes) == 1:
+            # stack mode: the plane's own trackers are the result (pdl_inference3d.py:222-223)
+            return sharded.plane_volume(planes['xy'], labels, thing_list, min_size, min_span, group=group)
+        cons, vols, zs = sharded.consensus_volume(planes, shape3d, labels, thing_list, pixel_vote_thr, cluster_iou_thr,
+                                                  bypass, min_size, min_span, group=group)
+        return vols, zs, {c: int(cons[c].alive.sum()) for c in labels}
+
+    if pipeline is not None:
+        return pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
+                            track=track, finish=finish, class_names=class_names, out=out)
     planes, base = {}, 0
     for axis in axes:
         n = dv.n_slices(axis)
         b = sharded.shard_bounds(n, world)
         lo, hi = int(b[rank]), int(b[rank + 1])
-        h, w = dv.plane_shape(axis)
         heads = _plane_heads(engine, dv, axis, lo, hi, batch_pixels, steps)
         pan = sharded.sharded_panoptic_stack(heads['sem'], heads['ctr_hmp'], heads['offsets'], group=group, **params)
         del heads
-        pan = pan[:, :h, :w].contiguous()
-        planes[axis] = sharded.track_plane(pan, axis, shape3d, labels, thing_list, div, merge_iou_thr, merge_ioa_thr,
-                                           inst_base=base, group=group)
+        planes[axis] = track(pan, axis, base)
         base += planes[axis].n_inst
         del pan
-    if len(axes) == 1:
-        # stack mode: the plane's own trackers are the result (pdl_inference3d.py:222-223)
-        assert axes[0] == 'xy', "stack mode runs along z (axes=('xy',))"
-        vols, (z0, z1), counts = sharded.plane_volume(planes['xy'], labels, thing_list, min_size, min_span, group=group)
-    else:
-        cons, vols, (z0, z1) = sharded.consensus_volume(planes, shape3d, labels, thing_list, pixel_vote_thr,
-                                                        cluster_iou_thr, bypass, min_size, min_span, group=group)
-        counts = {c: int(cons[c].alive.sum()) for c in labels}
+    vols, (z0, z1), counts = finish(planes)
     datasets = {c: None for c in labels}
     if out is not None:
         names = {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}

@@ -34,6 +34,7 @@ class GraphedForward(torch.nn.Module):
         # graph, which is enough for a consumer that reads them on the same stream before calling again (bench.py)
         self.clone_outputs = bool(clone_outputs)
         self._graphs = {}
+        self.captures = 0                            # graphs captured so far (evictions make this exceed len(_graphs))
 
     def parameters(self, recurse=True):              # engines look the device up through the first parameter
         return self.model.parameters(recurse)
@@ -72,10 +73,11 @@ class GraphedForward(torch.nn.Module):
             if len(self._graphs) >= self.max_graphs:
                 self._graphs.pop(next(iter(self._graphs)))
             entry = self._graphs[key] = self._capture(x, args, kwargs)
+            self.captures += 1
         graph, static_in, static_out = entry
         if x.data_ptr() != static_in.data_ptr():      # a caller that filled input_buffer() in place skips this copy
             static_in.copy_(x)
         graph.replay()
         if not self.clone_outputs:
             return dict(static_out)
-        return {k: v.clone() for k, v in static_out.items()}
+        return {k: v.clone() if torch.is_tensor(v) else v for k, v in static_out.items()}

@@ -573,13 +573,22 @@ class PanopticDeepLab(nn.Module):
         # scale_factor=4 with align_corners=True: out = 4 * in, src = dst * (in - 1) / (out - 1)
         return _up_bilinear(x, (4 * x.shape[2], 4 * x.shape[3]), self.hip_ops)
 
+    # inference only, set by inference.pipeline.VolumePipeline on the fp32 GPU path: forward returns the quarter-resolution
+    # tensor of every head it would have passed through _up4 and names those heads under 'deferred_up4'; the caller
+    # finishes them with emp_upsample_bilinear_prob, straight into the buffer the post-processing reads
+    defer_up4 = False
+
+    def _finish(self, heads, up):
+        if not self.defer_up4:
+            return {k: self._up4(v) if k in up else v for k, v in heads.items()}
+        return dict(heads, deferred_up4=tuple(up))
+
     def forward(self, x):
         pyramid = self.encoder(x)
         sem_x = self.semantic_decoder(pyramid)
         ins_x = sem_x if self.instance_decoder is None else self.instance_decoder(pyramid)
-        return {'sem_logits': self._up4(self.semantic_head(sem_x)),
-                'ctr_hmp': self._up4(self.ins_center(ins_x)),
-                'offsets': self._up4(self.ins_xy(ins_x))}
+        return self._finish({'sem_logits': self.semantic_head(sem_x), 'ctr_hmp': self.ins_center(ins_x),
+                             'offsets': self.ins_xy(ins_x)}, ('sem_logits', 'ctr_hmp', 'offsets'))
 
 
 # ----------------------------------------------------------------------------- PointRend (inference)
@@ -712,10 +721,8 @@ class PanopticDeepLabPR(PanopticDeepLab):
         # PointRend: on the GPU the features stay NHWC (emp_pr_point_sample gathers whole pixels); the library path
         # makes them NCHW-contiguous itself
         sem = self.semantic_pr(self.semantic_head(sem_x).float().contiguous(), sem_x.float())
-        ctr, off = self.ins_center(ins_x), self.ins_xy(ins_x)
-        return {'sem_logits': sem['sem_seg_logits'],
-                'ctr_hmp': self._up4(ctr) if interpolate_ins else ctr,
-                'offsets': self._up4(off) if interpolate_ins else off}
+        return self._finish({'sem_logits': sem['sem_seg_logits'], 'ctr_hmp': self.ins_center(ins_x),
+                             'offsets': self.ins_xy(ins_x)}, ('ctr_hmp', 'offsets') if interpolate_ins else ())
 
 
 # ----------------------------------------------------------------------------- deployment helpers

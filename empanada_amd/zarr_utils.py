@@ -354,6 +354,12 @@ class SlabWriter:
         self.turn = 0
         self.np_dtype = array.dtype
 
+    def retarget(self, array, z0):
+        """write the following slabs into another array of the same slab shape and dtype (the pool and the pinned
+        buffers are kept: pinning is slow); pending writes into the previous array are finished first"""
+        self.drain()
+        self.array, self.z0, self.np_dtype = array, int(z0), array.dtype
+
     def next_buffer(self):
         """a pinned buffer that is safe to overwrite (its previous files are on disk)"""
         i = self.turn

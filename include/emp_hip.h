@@ -304,6 +304,18 @@ int emp_stem_conv7_bn_relu_maxpool(const float *x, const float *w_tc, const floa
  *         cases -- tests/test_pipeline_gpu.py).  logits, prob: planar (N, C, HW) fp32; may alias.               */
 int emp_logits_to_prob(const float *logits, int N, int C, int64_t HW, float *prob, void *stream);
 
+/* ---- D3 + D2: the x4 up-sampling of a head fused with logits_to_prob ----------------------------------------
+ * replaces F.interpolate(scale_factor=4, bilinear, align_corners=True) of a head
+ *                                                   empanada/models/panoptic_deeplab.py:100-113
+ *          followed by logits_to_prob               empanada/inference/engines.py:22-30
+ * x, y, the strides and the bilinear arithmetic as in emp_upsample_bilinear (D3).  prob == 0: y is exactly what
+ * emp_upsample_bilinear writes.  prob == 1: y = emp_logits_to_prob (D2) of that value in the same launch -- sigmoid for
+ * C == 1, softmax over the C <= 64 channels of a pixel otherwise; the same operations in the same order, so bit-identical
+ * to the two calls one after the other, without the full-resolution logits ever being written.  y is typically the
+ * [s, e) slice view of a plane's resident head buffer; it must not alias x.                                        */
+int emp_upsample_bilinear_prob(const float *x, int N, int C, int h, int w, const int64_t *x_strides,
+                               float *y, int H, int W, const int64_t *y_strides, int prob, void *stream);
+
 /* ---- P1 + P2: recursive median over a resident stack, fused with hardening ----------------
  * replaces _MedianQueue.get_next/get_median/end   empanada/inference/engines.py:47-90
  *          _harden_seg / harden_seg               engines.py:114-121, inference/patterns.py:242-251
