@@ -262,6 +262,8 @@ def find_centers(hmp, thr, k, cap=1024):
     """hmp (D,h,w) fp32 -> idx (D,cap) int32 raster-sorted, count (D) int32."""
     require_gpu()
     _expect("find_centers: heat map", hmp, torch.float32)
+    if not float(thr) >= 0.0:
+        raise HipError(f"find_centers: the threshold must be >= 0 (got {thr})")
     D, h, w = hmp.shape
     hmp = hmp.contiguous()
     idx = torch.empty((D, cap), dtype=torch.int32, device=hmp.device)
@@ -275,6 +277,8 @@ def find_centers_ws(hmp, thr, k, cap):
     count is exact; idx holds the first min(count, cap) centres of each slice in raster order."""
     require_gpu()
     _expect("find_centers_ws: heat map", hmp, torch.float32)
+    if not float(thr) >= 0.0:
+        raise HipError(f"find_centers_ws: the threshold must be >= 0 (got {thr})")
     D, h, w = hmp.shape
     hmp = hmp.contiguous()
     cap = int(cap)

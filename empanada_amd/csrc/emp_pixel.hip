@@ -520,6 +520,7 @@ extern "C" int emp_find_centers(const float *hmp, int D, int h, int w, float thr
                                 int32_t *out_idx, int32_t *out_count, void *stream)
 {
     EMP_REQUIRE(hmp && out_idx && out_count, "find_centers: null pointer");
+    EMP_REQUIRE(thr >= 0.0f, "find_centers: the threshold must be >= 0 (got %g)", (double)thr);
     EMP_REQUIRE(k >= 1 && k <= CT_MAXK, "find_centers: nms kernel %d not in 1..%d", k, CT_MAXK);
     EMP_REQUIRE(cap >= 1 && cap <= EMP_MAX_CENTERS, "find_centers: cap %d not in 1..%d", cap, EMP_MAX_CENTERS);
     EMP_REQUIRE(D >= 0 && D <= 65535 && h > 0 && w > 0, "find_centers: bad shape D=%d h=%d w=%d", D, h, w);
@@ -628,6 +629,7 @@ extern "C" int emp_find_centers_ws(const float *hmp, int D, int h, int w, float 
                                    int32_t *out_idx, int32_t *out_count, void *stream)
 {
     EMP_REQUIRE(hmp && work && out_idx && out_count, "find_centers_ws: null pointer");
+    EMP_REQUIRE(thr >= 0.0f, "find_centers_ws: the threshold must be >= 0 (got %g)", (double)thr);
     EMP_REQUIRE(k >= 1 && k <= CT_MAXK, "find_centers_ws: nms kernel %d not in 1..%d", k, CT_MAXK);
     EMP_REQUIRE(cap >= 1 && cap <= EMP_CENTER_LIMIT, "find_centers_ws: cap %d not in 1..%d", cap, EMP_CENTER_LIMIT);
     EMP_REQUIRE(D >= 0 && D <= 65535 && h > 0 && w > 0, "find_centers_ws: bad shape D=%d h=%d w=%d", D, h, w);
@@ -1008,7 +1010,7 @@ __global__ __launch_bounds__(256) void fuse_hist_kernel(const uint8_t *__restric
             if (c >= nc) c = nc - 1;
             int y = (int)(p / W), x = (int)(p % W);
             int id = g[(int64_t)(y / up) * w + x / up];
-            ins = ((thing_mask >> c) & 1u) ? id : 0;
+            ins = (((thing_mask >> c) & 1u) && id <= cap) ? id : 0;   // ids above cap count as 0 (emp_hip.h)
         }
         wave_hist_add(bh, (int64_t)ins * nc + c, live && ins > 0);
         wave_hist_add(bs, (int64_t)c, live && ins == 0);
@@ -1095,7 +1097,7 @@ __global__ __launch_bounds__(256) void fuse_apply_kernel(const uint8_t *__restri
         if (c >= nc) c = nc - 1;
         int y = (int)(p / W), x = (int)(p % W);
         int id = g[(int64_t)(y / up) * w + x / up];
-        int ins = ((thing_mask >> c) & 1u) ? id : 0;
+        int ins = (((thing_mask >> c) & 1u) && id <= cap) ? id : 0;
         int64_t v;
         if (ins > 0) v = (int64_t)ll[ins];
         else v = oo[c] ? (int64_t)c * div : void_label;
@@ -1138,7 +1140,7 @@ __global__ __launch_bounds__(256) void fuse_apply_vec4_kernel(const uint8_t *__r
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             int c = cls[j] < nc ? cls[j] : nc - 1;
-            int ins = ((thing_mask >> c) & 1u) ? id[j] : 0;
+            int ins = (((thing_mask >> c) & 1u) && id[j] <= cap) ? id[j] : 0;
             int64_t v = ins > 0 ? (int64_t)ll[ins] : (oo[c] ? (int64_t)c * div : void_label);
             r[j] = (OutT)v;
         }
@@ -1207,7 +1209,7 @@ __global__ __launch_bounds__(256) void fuse_apply_multi_kernel(const uint8_t *__
                     c = c < (uint32_t)nc ? c : (uint32_t)(nc - 1);
                     const uint32_t id = ((j < 2 ? iw[u].x : iw[u].y) >> (16 * (j & 1))) & 0xffffu;
                     uint32_t v = ((okmask >> c) & 1u) ? c * udiv : vlab;
-                    if (((thing_mask >> c) & 1u) && id > 0) v = ll[id];
+                    if (((thing_mask >> c) & 1u) && id > 0 && id <= (uint32_t)cap) v = ll[id];
                     r[j] = v;
                 }
                 *reinterpret_cast<uint4 *>(o + q * 4) = make_uint4(r[0], r[1], r[2], r[3]);
@@ -1266,6 +1268,7 @@ __global__ __launch_bounds__(256) void fuse_hist_vec4_kernel(const uint8_t *__re
         for (int j = 0; j < 4; ++j) {
             cls[j] = (int)((cw[0] >> (8 * j)) & 0xffu);
             id[j] = (int)(((j < 2 ? iw[0].x : iw[0].y) >> (16 * (j & 1))) & 0xffffu);
+            if (id[j] > cap) id[j] = 0;                                   // ids above cap count as 0 (emp_hip.h)
         }
         cw[0] = cw[1]; iw[0] = iw[1];
         cw[1] = cw[2]; iw[1] = iw[2];

@@ -323,7 +323,9 @@ int emp_upsample_bilinear_prob(const float *x, int N, int C, int h, int w, const
  * median of {out[s-m..s-1], prob[s..s+m]} (the reference writes the median back into its queue,
  * which makes the filter recursive); the first and last m slices pass through.  Requires
  * D >= ks or ks == 1 (the reference loses slices for shorter stacks; the host mirrors that).
- * out_sem (D, HW) u8: C == 1 -> (p >= thr), C > 1 -> argmax over the filtered channels.
+ * out_sem (D, HW) u8: C == 1 -> (p >= thr), C > 1 -> argmax over the filtered channels (first
+ * maximum wins); thr is not used for C > 1.  C > 1 keeps C * ks * 1 KiB of filter windows in LDS:
+ * above 160 KiB (C * ks > 160) the call fails with EMP_EINVAL.
  * out_prob (D, C, HW) fp32 or NULL: the filtered probabilities.                                */
 int emp_median_harden_stack(const float *prob, int D, int C, int64_t HW, int ks, float thr,
                             uint8_t *out_sem, float *out_prob, void *stream);
@@ -333,7 +335,8 @@ int emp_median_harden_stack(const float *prob, int D, int C, int64_t HW, int ks,
  * replaces _MedianQueue.get_median                 engines.py:59-66                             */
 int emp_median_step(const float *const *slices_host, int ks, int64_t n, float *out, void *stream);
 
-/* Harden only (no median).  prob (D, C, HW) -> out_sem (D, HW) u8.                              */
+/* Harden only (no median): emp_median_harden_stack with ks = 1.  prob (D, C, HW) -> out_sem (D, HW) u8;
+ * thr is not used for C > 1.                                                                    */
 int emp_harden(const float *prob, int D, int C, int64_t HW, float thr, uint8_t *out_sem,
                void *stream);
 
@@ -343,13 +346,16 @@ int emp_harden(const float *prob, int D, int C, int64_t HW, float thr, uint8_t *
  * threshold(v) over the k x k window rows y-k/2 .. y-k/2+k-1 (same for x; -inf padding).
  * out_idx (D, cap) int32 flat indices y*w+x, ascending (raster order) per slice;
  * out_count (D) int32 = number found (may exceed cap: then only `cap` are stored, unordered
- * selection -- the caller must treat count > cap as an error).  cap <= EMP_MAX_CENTERS.         */
+ * selection -- the caller must treat count > cap as an error).  cap <= EMP_MAX_CENTERS.
+ * thr must be >= 0 (EMP_EINVAL otherwise): the streaming test "v > thr and v > 0" and its
+ * comparison of raw neighbours are only proven equal to the reference's for a non-negative
+ * threshold, and no configuration uses a negative one.                                          */
 int emp_find_centers(const float *hmp, int D, int h, int w, float thr, int k, int cap,
                      int32_t *out_idx, int32_t *out_count, void *stream);
 
 /* The same detection for any capacity 1 <= cap <= EMP_CENTER_LIMIT (no in-LDS sort)
  * replaces find_instance_center                    empanada/inference/postprocess.py:38-76
- * Same rule as emp_find_centers.  The centres of a slice are marked in a bitmap (one bit per pixel)
+ * Same rule as emp_find_centers, thr >= 0 included.  The centres of a slice are marked in a bitmap (one bit per pixel)
  * and written out in one ordered pass, so
  *   out_count (D) int32 = exact number found, whatever cap is;
  *   out_idx (D, cap) int32 = the FIRST min(count, cap) centres of each slice in raster order
@@ -384,6 +390,8 @@ int emp_group_pixels(const int32_t *ctr_idx, const int32_t *ctr_count, int cap,
  *          merge_semantic_and_instance             postprocess.py:223-296
  * sem (D, H, W) u8 class ids (< n_classes <= EMP_MAX_CLASSES); ids (D, H/up, W/up) u16 in 0..cap
  * (nearest-upsampled by `up` on the fly); thing_mask bit c set = class c is a thing.
+ * An id above cap counts as 0 (no instance) in every pass, so no id reads or writes past a slice's
+ * tables; a class value >= n_classes counts as n_classes - 1.
  * Per instance id (ascending) with >= 1 thing pixel: class = most frequent class among its thing
  * pixels (ties -> smallest), new id = per-class counter from 1, pan = class*div + new id.
  * Non-thing classes: pixels with instance 0 get class*div when their count >= stuff_area.
