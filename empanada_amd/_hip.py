@@ -363,8 +363,16 @@ class RunTable:
 
 
 def extract_runs(pan, label_divisor, cc_classes):
-    """pan (D,H,W) uint32 cuda -> RunTable (device tensors; two small host syncs for the counts)."""
+    """pan (D,H,W) uint32 cuda -> RunTable (device tensors; two small host syncs for the counts).  cc_classes: the
+    classes split into 8-connected components, each in 0..31 (the cc_mask of emp_runs_label has 32 bits; a class
+    beyond them would silently be grouped by value instead, so it is refused)."""
     require_gpu()
+    mask = 0
+    for c in cc_classes:
+        if not 0 <= int(c) < 32:
+            raise ValueError(f"extract_runs: connected-component class {int(c)} is outside 0..31 (emp_runs_label "
+                             "takes a 32-bit class mask)")
+        mask |= 1 << int(c)
     D, H, W = pan.shape
     pan = pan.contiguous()
     dev = pan.device
@@ -378,9 +386,6 @@ def extract_runs(pan, label_divisor, cc_classes):
     t.r_len = torch.empty_like(t.r_start)
     t.r_val = torch.empty((max(n_runs, 1),), dtype=torch.uint32, device=dev)
     call('emp_runs_extract', _ptr(pan), D, H, W, _ptr(offs), _ptr(t.r_start), _ptr(t.r_len), _ptr(t.r_val), stream())
-    mask = 0
-    for c in cc_classes:
-        mask |= 1 << int(c)
     work = torch.empty((query('emp_runs_label_work_elems', n_runs),), dtype=torch.int32, device=dev)
     m = max(n_runs, 1)
     t.r_comp = torch.empty((m,), dtype=torch.int32, device=dev)
@@ -472,7 +477,20 @@ def rle_pair_intersections(starts, lens, inst_off, pairs):
     return out
 
 
+def fill_ids_to_dev(ids):
+    """host instance ids -> uint32 device tensor for fill_runs_u32.  emp_fill_runs_u32 tags voxels with bit 31 between
+    its two passes, so an id of 2^31 or more (or a negative one, which wraps to such a value) would make the second
+    pass index `ids` out of bounds: refused here, before any launch."""
+    import numpy as np
+    a = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 31):
+        raise ValueError("fill: ids must be < 2^31 and the volume at most 32-bit")
+    return np_to_dev_u32(a)
+
+
 def fill_runs_u32(vol, starts, lens, order, ids):
+    """ids: device tensor of values < 2^31 (host ids go through fill_ids_to_dev, which checks them); vol must hold no
+    value of 2^31 or more under a run (a fresh volume, or one painted by this function)."""
     require_gpu()
     _expect("fill_runs_u32: volume", vol, (torch.uint32, torch.int32))
     n = _expect("fill_runs_u32: starts", starts, torch.int64).numel()
@@ -595,6 +613,8 @@ def rle_decode(starts, runs):
     csum = torch.cumsum(runs, 0)
     off = (csum - runs).contiguous()
     out = torch.empty((int(csum[-1].item()),), dtype=torch.int64, device=starts.device)
+    if out.numel() == 0:                 # zero-length runs only: nothing to write (and no output pointer to pass)
+        return out
     call('emp_rle_decode', _ptr(starts.contiguous()), _ptr(runs.contiguous()), _ptr(off), n, _ptr(out), stream())
     return out
 

@@ -252,7 +252,7 @@ def numpy_fill_instances(volume, instances):
     order = np.repeat(np.arange(len(ids), dtype=np.int32), [len(s) for s in starts])
     flat = volume.reshape(-1)
     top = int(flat.max()) if flat.size else 0
-    if volume.dtype.itemsize > 4 or int(max(ids)) >= 2 ** 31 or top >= 2 ** 31:
+    if volume.dtype.itemsize > 4 or int(max(ids)) >= 2 ** 31 or int(min(ids)) < 0 or top >= 2 ** 31:
         raise ValueError("fill: ids must be < 2^31 and the volume at most 32-bit")
     if top > 0 or (volume.dtype.kind == 'i' and flat.size and int(flat.min()) < 0):
         dvol = _hip.np_to_dev_u32(flat)

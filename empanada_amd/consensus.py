@@ -132,10 +132,12 @@ class ConsensusResult:
                 out[i + 1] = {'box': tuple(int(x) for x in self.boxes[i]), 'starts': r[:, 0], 'runs': r[:, 1] - r[:, 0]}
         return out
 
-    def paint(self, vol_flat, lo=0, ids=None):
+    def paint(self, vol_flat, lo=0, ids=None, fresh=False):
         """write ids[i] (default i + 1; uint32 device volume, or uint8 with one value) over the voxels of every
         surviving instance; vol_flat covers the flat voxel interval starting at lo.  Later instances overwrite
-        earlier ones (fill_volume, patterns.py:204-220)."""
+        earlier ones (fill_volume, patterns.py:204-220).  uint32: ids and the volume's earlier contents must be below
+        2^31 (emp_fill_runs_u32), else ValueError before any launch; fresh=True says the volume is all zero and
+        saves looking at it."""
         m = int(self.off[-1]) if len(self.off) else 0
         if m == 0 or not self.alive.any():
             return vol_flat
@@ -147,12 +149,14 @@ class ConsensusResult:
             _hip.fill_runs_u8(vol_flat, st[keep].contiguous(), ln[keep].contiguous(), 1 if ids is None else int(ids))
             return vol_flat
         val = np.arange(1, self.n + 1, dtype=np.int64) if ids is None else np.asarray(ids, dtype=np.int64)
-        val = np.where(self.alive, val, 0)
+        dev_ids = _hip.fill_ids_to_dev(np.where(self.alive, val, 0))
+        if not fresh and vol_flat.numel() and int(vol_flat.view(torch.int32).min()) < 0:
+            raise ValueError("fill: ids must be < 2^31 and the volume at most 32-bit")
         order = torch.empty((m,), dtype=torch.int32, device=dev)
         off_d = torch.from_numpy(self.off).to(dev)
         iota = torch.arange(self.n, dtype=torch.int32, device=dev)
         _hip.call('emp_track_expand', _hip._ptr(off_d), _hip._ptr(iota), self.n, m, _hip._ptr(order), _hip.stream())
-        _hip.fill_runs_u32(vol_flat, st, ln, order, _hip.np_to_dev_u32(val))
+        _hip.fill_runs_u32(vol_flat, st, ln, order, dev_ids)
         return vol_flat
 
 

@@ -3,6 +3,7 @@
 #include "emp_common.h"
 
 #include <hipcub/hipcub.hpp>
+#include <rocprim/rocprim.hpp>
 
 extern "C" int emp_exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out, int32_t *tmp, void *stream);
 extern "C" int64_t emp_scan_tmp_elems(int64_t n);
@@ -10,14 +11,33 @@ extern "C" int64_t emp_scan_tmp_elems(int64_t n);
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------
+// rocPRIM's radix sort takes a merge-sort path for 1024 < n <= 2^20 whose comparison mask is built from
+// T(1) << end_bit: undefined for end_bit == 64, and on the host that builds it the mask comes out as the bits BELOW
+// begin_bit.  A sort over [begin_bit, 64) with begin_bit > 0 then merges blocks that were sorted by other bits, and
+// leaves part of the output unwritten.  Such bit ranges are sorted with a configuration that has no merge-sort path
+// (single block up to 1024 items, Onesweep above); every other range goes through hipCUB as before.
+using SortNoMerge = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
+                                               rocprim::default_config, 0>;
+
+static hipError_t sort_pairs(void *work, size_t &bytes, const uint64_t *keys_in, uint64_t *keys_out,
+                             const int32_t *vals_in, int32_t *vals_out, int n, int begin_bit, int end_bit,
+                             hipStream_t st)
+{
+    if (begin_bit > 0 && end_bit == 64)
+        return rocprim::radix_sort_pairs<SortNoMerge>(work, bytes, keys_in, keys_out, vals_in, vals_out, n,
+                                                      (unsigned)begin_bit, (unsigned)end_bit, st);
+    return hipcub::DeviceRadixSort::SortPairs(work, bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit,
+                                              st);
+}
+
 extern "C" int64_t emp_sort_work_bytes(int64_t n)
 {
-    size_t bytes = 0;
+    size_t bytes = 0, bytes_upper = 0;
     if (n < 1) n = 1;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
-                                           (const int32_t *)nullptr, (int32_t *)nullptr, (int)n, 0, 64,
-                                           (hipStream_t)0) != hipSuccess)
+    if (sort_pairs(nullptr, bytes, nullptr, nullptr, nullptr, nullptr, (int)n, 0, 64, (hipStream_t)0) != hipSuccess ||
+        sort_pairs(nullptr, bytes_upper, nullptr, nullptr, nullptr, nullptr, (int)n, 1, 64, (hipStream_t)0) != hipSuccess)
         return -1;
+    if (bytes_upper > bytes) bytes = bytes_upper;
     return (int64_t)align_up((int64_t)bytes, 256) + 256;
 }
 
@@ -30,12 +50,11 @@ extern "C" int emp_sort_u64_i32(const uint64_t *keys_in, uint64_t *keys_out, con
     EMP_REQUIRE(keys_in && keys_out && vals_in && vals_out && work, "sort: null pointer");
     EMP_REQUIRE(begin_bit >= 0 && end_bit <= 64 && begin_bit < end_bit, "sort: bad bit range");
     size_t need = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit,
-                                       end_bit, emp_stream(stream));
+    sort_pairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit, end_bit, emp_stream(stream));
     EMP_REQUIRE((int64_t)need <= work_bytes, "sort: workspace too small (%lld < %zu)", (long long)work_bytes, need);
     size_t wb = (size_t)work_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(work, wb, keys_in, keys_out, vals_in, vals_out, (int)n,
-                                                      begin_bit, end_bit, emp_stream(stream));
+    hipError_t e = sort_pairs(work, wb, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit, end_bit,
+                              emp_stream(stream));
     if (e != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "sort: %s", hipGetErrorString(e));
     return EMP_OK;
 }

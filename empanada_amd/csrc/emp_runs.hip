@@ -466,9 +466,9 @@ extern "C" int emp_runs_label(const int32_t *r_start, const int32_t *r_len, cons
     int64_t n_rows = (int64_t)D * H;
     int grid = emp_grid(n_runs, 256, 4096);
     hipLaunchKernelGGL(label_init_kernel, dim3(grid), dim3(256), 0, st, n_runs, n_rows, row_offsets, parent, row);
-    bool any_plain = false;
-    // classes beyond bit 31 and classes whose bit is clear are "plain" (grouped by value)
-    any_plain = (cc_mask != 0xffffffffu);
+    // classes beyond bit 31 and classes whose bit is clear are "plain" (grouped by value): the grouping pass can be
+    // left out only when every bit is set AND no uint32 value has a class of 32 or more
+    const bool any_plain = (cc_mask != 0xffffffffu) || (0xffffffffLL / label_divisor >= 32);
     if (any_plain) {
         if (hipMemsetAsync(hkeys, 0, sizeof(unsigned long long) * L.hsize, st) != hipSuccess ||
             hipMemsetAsync(hvals, 0x7f, sizeof(int32_t) * L.hsize, st) != hipSuccess)

@@ -604,8 +604,8 @@ def fill_volume_device(shape3d, trackers, dtype=torch.uint32):
         return vol.reshape(shape3d)
     vol = torch.zeros((n,), dtype=torch.int32, device='cuda').view(torch.uint32)
     if ids and sum(len(s) for s in starts):
+        dev_ids = _hip.fill_ids_to_dev(ids)              # ValueError for an instance id of 2^31 or more, before any launch
         _hip.fill_runs_u32(vol, torch.from_numpy(np.concatenate(starts)).cuda(),
                            torch.from_numpy(np.concatenate(runs)).cuda(),
-                           torch.from_numpy(np.concatenate(order)).cuda(),
-                           _hip.np_to_dev_u32(np.asarray(ids, dtype=np.int64)))
+                           torch.from_numpy(np.concatenate(order)).cuda(), dev_ids)
     return vol.reshape(shape3d)

@@ -132,9 +132,9 @@ def rle_seg_to_pan_seg(rle_seg, shape):
     n = int(np.prod(shape))
     vol = torch.zeros((n,), dtype=torch.int32, device='cuda').view(torch.uint32)
     if ids and sum(len(s) for s in starts):
+        dev_ids = _hip.fill_ids_to_dev(ids)              # ValueError for an object id of 2^31 or more, before any launch
         dev = lambda x, dt: torch.from_numpy(np.concatenate(x).astype(dt)).cuda()
-        _hip.fill_runs_u32(vol, dev(starts, np.int64), dev(runs, np.int64), dev(order, np.int32),
-                           _hip.np_to_dev_u32(np.asarray(ids, dtype=np.int64)))
+        _hip.fill_runs_u32(vol, dev(starts, np.int64), dev(runs, np.int64), dev(order, np.int32), dev_ids)
     return vol.cpu().numpy().reshape(shape)
 
 

@@ -466,7 +466,7 @@ def consensus_volume(planes, shape3d, labels, thing_list, pixel_vote_thr=2, clus
         vol = torch.zeros(((z1 - z0) * Y * X,), dtype=torch.int32 if thing else torch.uint8, device=dev)
         if thing:
             vol = vol.view(torch.uint32)
-        res.paint(vol, lo)
+        res.paint(vol, lo, fresh=True)
         cons[class_id] = res
         vols[class_id] = vol.reshape(z1 - z0, Y, X)
     return cons, vols, (z0, z1)
@@ -499,11 +499,11 @@ def plane_volume(pt, labels, thing_list, min_size=None, min_span=None, group=Non
         if n and keep.any():
             st = (pt.st[:n] - z0 * Y * X).contiguous()
             if thing:
+                dev_ids = _hip.fill_ids_to_dev(np.where(keep, pt.inst_label, 0))     # ValueError for labels >= 2^31
                 order = torch.empty((n,), dtype=torch.int32, device=dev)
                 iota = torch.arange(pt.n_inst, dtype=torch.int32, device=dev)
                 _hip.call('emp_track_expand', _hip._ptr(off), _hip._ptr(iota), pt.n_inst, n, _hip._ptr(order), _hip.stream())
-                _hip.fill_runs_u32(vol.view(torch.uint32), st, pt.ln[:n].contiguous(), order,
-                                   _hip.np_to_dev_u32(np.where(keep, pt.inst_label, 0)))
+                _hip.fill_runs_u32(vol.view(torch.uint32), st, pt.ln[:n].contiguous(), order, dev_ids)
             else:
                 flag = torch.empty((n,), dtype=torch.int32, device=dev)
                 kd = torch.from_numpy(keep.astype(np.int32)).to(dev)

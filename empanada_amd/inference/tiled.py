@@ -51,12 +51,13 @@ def _paint(rle_seg, shape, out):
             ids.append(int(object_id))
             starts.append(np.asarray(a['starts'], dtype=np.int64))
             runs.append(np.asarray(a['runs'], dtype=np.int64))
+    dev_ids = _hip.fill_ids_to_dev(ids)                  # ValueError for an object id of 2^31 or more, before any launch
     flat = out.view(torch.int32).reshape(-1)
     flat.zero_()
     if ids and sum(len(s) for s in starts):
         cat = lambda x, dt: torch.from_numpy(np.concatenate(x).astype(dt)).to(out.device)
         _hip.fill_runs_u32(flat.view(torch.uint32), cat(starts, np.int64), cat(runs, np.int64), cat(order, np.int32),
-                           _hip.np_to_dev_u32(np.asarray(ids, dtype=np.int64)))
+                           dev_ids)
 
 
 def _overlap_prefix(tiler, device):
@@ -228,9 +229,9 @@ def stitch_stack(tables, tiler, n_slices, labels, thing_list, label_divisor, use
     run_z = torch.empty((n_runs,), dtype=torch.int32, device=dev)
     _hip.call('emp_track_expand', _hip._ptr(off), _hip._ptr(node_z), N, n_runs, _hip._ptr(run_z), _hip.stream())
     hw = H * W
+    dev_ids = _hip.fill_ids_to_dev(new_id)               # labels of 2^31 or more cannot be painted: ValueError
     ln_cut = torch.minimum(ln, torch.clamp(hw - st, min=0))
-    _hip.fill_runs_u32(out.view(torch.uint32).reshape(-1), st + run_z.to(torch.int64) * hw, ln_cut, run_cl,
-                       _hip.np_to_dev_u32(new_id))
+    _hip.fill_runs_u32(out.view(torch.uint32).reshape(-1), st + run_z.to(torch.int64) * hw, ln_cut, run_cl, dev_ids)
     rles = None
     if return_rle:
         rles = _cluster_rle_segs(st, ln, run_cl, n_cl, kept, new_id, cl_of, cl_seg, node, labels, n_slices)

@@ -425,7 +425,13 @@ int emp_fuse_apply(const uint8_t *sem, const uint16_t *ids, int D, int H, int W,
  * Step 4  emp_runs_label: union-find over runs.  Classes whose bit is set in cc_mask are split
  *         into 8-connected components of equal value and renumbered class*div + k, k = 1.. in
  *         raster order of the component's first pixel, per slice; runs of other classes keep
- *         their value as label (one instance per distinct value).  Outputs, per run:
+ *         their value as label (one instance per distinct value).  cc_mask has one bit per class
+ *         0..31: a class of 32 or more (value / label_divisor >= 32) is always grouped by value,
+ *         whatever the mask, 0xffffffff included.  The Python wrapper (_hip.extract_runs) refuses
+ *         a connected-component class outside 0..31 with ValueError rather than group it silently.
+ *         k is not limited by label_divisor: the k-th component of a class gets class*div + k even
+ *         where k >= div; the class of a component is that of its ORIGINAL value (r_val[c_first]).
+ *         Outputs, per run:
  *         r_comp (int32) = dense component index over the whole stack (ordered by first run),
  *         and per component: c_slice, c_label (int64), c_area (int64), c_box (4 x int32:
  *         y0, x0, y1, x1 half-open), c_first (first run).  n_comp_out (device int32[1]).
@@ -490,8 +496,11 @@ int emp_rle_pair_intersections(const int64_t *starts, const int64_t *lens, const
                                void *stream);
 
 /* ---- stable key/value radix sort (rocPRIM via hipCUB), used to order run tables --------------
- * keys 64-bit unsigned, values int32; bits [begin_bit, end_bit) are compared.
- * work: emp_sort_work_bytes(n) bytes.                                                          */
+ * keys 64-bit unsigned, values int32; bits [begin_bit, end_bit) are compared, 0 <= begin_bit <
+ * end_bit <= 64; keys that agree in those bits keep their input order, and keys_out holds the whole
+ * keys.  Every such range is supported for every n (a range [b, 64) with b > 0 is kept off rocPRIM's
+ * merge-sort path, whose comparison mask is wrong for end_bit == 64).
+ * work: emp_sort_work_bytes(n) bytes (enough for any bit range); a smaller one is refused.       */
 int64_t emp_sort_work_bytes(int64_t n);
 int emp_sort_u64_i32(const uint64_t *keys_in, uint64_t *keys_out, const int32_t *vals_in,
                      int32_t *vals_out, int64_t n, int begin_bit, int end_bit, void *work,
@@ -517,8 +526,14 @@ int emp_vote_ranges(const int64_t *starts, const int64_t *ends, const int32_t *g
  *          fill_func / zarr_fill_instances         empanada/zarr_utils.py:49-58,88-175
  * Runs (starts, lens int64 into the flat volume) carry an order index (position of their
  * instance in dict order) and ids[order] is painted; where runs of different instances overlap
- * the later instance wins, as in the reference's sequential fill.  Ids must be < 2^31; runs whose
- * id is 0 are skipped (an instance deleted by a filter neither paints nor shadows).              */
+ * the later instance wins, as in the reference's sequential fill.  Runs whose id is 0 are skipped
+ * (an instance deleted by a filter neither paints nor shadows).  Runs are cut at 0 and at n_vox.
+ * Ids must be < 2^31, and so must every value the volume already holds under a run: voxels are
+ * tagged with bit 31 between the two passes, and a value with that bit set would be taken for a
+ * tag and index `ids` out of bounds.  The kernel does not check this.  Every Python caller that
+ * takes ids or a volume from outside does, on the host, and raises ValueError before any launch
+ * (_hip.fill_ids_to_dev, array_utils.numpy_fill_instances, ConsensusResult.paint).  Voxels outside
+ * the runs are left as they are.                                                                  */
 int emp_fill_runs_u32(uint32_t *vol, int64_t n_vox, const int64_t *starts, const int64_t *lens,
                       const int32_t *order, int64_t n_runs, const uint32_t *ids, void *stream);
 int emp_fill_runs_u8(uint8_t *vol, int64_t n_vox, const int64_t *starts, const int64_t *lens,

@@ -38,6 +38,32 @@ def lift_xy_xz(axis, r_start, r_len, r_comp, c_slice, comp_inst, H, W, Y, X, sli
     return np.array(keys, dtype=np.uint64), np.array(lens, dtype=np.int64)
 
 
+def lift_tile(r_start, r_len, r_comp, c_slice, comp_inst, tw, X, y0, x0, inst_base=0):
+    """Tiler.translate_rle_seg (tile.py:122-168) for the run table of one tile's slices.  Per (object, slice) the
+    reference holds the RLE of the object's flat TILE indices (array_utils.py:209-235: a run that ends at the tile's
+    last column goes on at column 0 of the next row), moves every START into the image frame, (start // tw + y0) * X +
+    start % tw + x0, and keeps the length.  Positions stay 2D.  Returns (key, length) in table order of the run heads."""
+    keys, lens = [], []
+    n = len(r_start)
+    i = 0
+    while i < n:
+        inst = comp_inst[r_comp[i]]
+        if inst < 0:
+            i += 1
+            continue
+        sl = c_slice[r_comp[i]]
+        start, length = int(r_start[i]), int(r_len[i])
+        j = i + 1
+        while (j < n and comp_inst[r_comp[j]] == inst and c_slice[r_comp[j]] == sl
+               and int(r_start[j - 1]) + int(r_len[j - 1]) == int(r_start[j])):
+            length += int(r_len[j])
+            j += 1
+        keys.append(((inst_base + int(inst)) << POS_BITS) | ((start // tw + y0) * X + start % tw + x0))
+        lens.append(length)
+        i = j
+    return np.array(keys, dtype=np.uint64), np.array(lens, dtype=np.int64)
+
+
 def lift_yz(vol_inst_plus1, X, x0=0, inst_base=0):
     """tracker.py:83-88 + 110-113: every pixel becomes a unit run at (z, y, slice) and finish() sorts and re-encodes,
     i.e. the RLE along x of the dense labelling.  vol_inst_plus1: (Z, Y, Xl) array of instance + 1 (0 = nothing) of the
