@@ -356,6 +356,22 @@ def exclusive_scan_i32(x):
     return out
 
 
+def row_runs(vol):
+    """vol (D,H,W) uint32 cuda, contiguous -> (row_offsets, n, r_start, r_len, r_val): the runs along the last axis
+    in raster order (count, scan, extract; one host sync for n).  The run arrays hold max(n, 1) elements."""
+    D, H, W = vol.shape
+    dev = vol.device
+    rows = torch.empty((D * H,), dtype=torch.int32, device=dev)
+    call('emp_runs_count', _ptr(vol), D, H, W, _ptr(rows), stream())
+    offs = exclusive_scan_i32(rows)
+    n = int(offs[-1].item())
+    r_start = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    r_len = torch.empty_like(r_start)
+    r_val = torch.empty((max(n, 1),), dtype=torch.uint32, device=dev)
+    call('emp_runs_extract', _ptr(vol), D, H, W, _ptr(offs), _ptr(r_start), _ptr(r_len), _ptr(r_val), stream())
+    return offs, n, r_start, r_len, r_val
+
+
 class RunTable:
     """Result of extract_runs(): SoA run table + components of a (D,H,W) uint32 label stack."""
     __slots__ = ('D', 'H', 'W', 'n_runs', 'n_comp', 'row_offsets', 'r_start', 'r_len', 'r_val', 'r_comp',
@@ -376,16 +392,9 @@ def extract_runs(pan, label_divisor, cc_classes):
     D, H, W = pan.shape
     pan = pan.contiguous()
     dev = pan.device
-    rows = torch.empty((D * H,), dtype=torch.int32, device=dev)
-    call('emp_runs_count', _ptr(pan), D, H, W, _ptr(rows), stream())
-    offs = exclusive_scan_i32(rows)
-    n_runs = int(offs[-1].item())
     t = RunTable()
+    offs, n_runs, t.r_start, t.r_len, t.r_val = row_runs(pan)
     t.D, t.H, t.W, t.n_runs, t.row_offsets = D, H, W, n_runs, offs
-    t.r_start = torch.empty((max(n_runs, 1),), dtype=torch.int32, device=dev)
-    t.r_len = torch.empty_like(t.r_start)
-    t.r_val = torch.empty((max(n_runs, 1),), dtype=torch.uint32, device=dev)
-    call('emp_runs_extract', _ptr(pan), D, H, W, _ptr(offs), _ptr(t.r_start), _ptr(t.r_len), _ptr(t.r_val), stream())
     work = torch.empty((query('emp_runs_label_work_elems', n_runs),), dtype=torch.int32, device=dev)
     m = max(n_runs, 1)
     t.r_comp = torch.empty((m,), dtype=torch.int32, device=dev)
@@ -586,14 +595,7 @@ def yz_runs_along_x(table, value_u32, shape3d, slice0=0):
     vol = torch.zeros((Z, Y, Xl), dtype=torch.int32, device=dev).view(torch.uint32)
     call('emp_scatter_yz_u32', _ptr(vol), Z, Y, Xl, _ptr(table.r_start), _ptr(table.r_len), _ptr(table.r_comp),
          _ptr(table.c_slice), _ptr(value_u32), table.n_runs, stream())
-    rows = torch.empty((Z * Y,), dtype=torch.int32, device=dev)
-    call('emp_runs_count', _ptr(vol), Z, Y, Xl, _ptr(rows), stream())
-    offs = exclusive_scan_i32(rows)
-    n = int(offs[-1].item())
-    r_start = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-    r_len = torch.empty_like(r_start)
-    r_val = torch.empty((max(n, 1),), dtype=torch.uint32, device=dev)
-    call('emp_runs_extract', _ptr(vol), Z, Y, Xl, _ptr(offs), _ptr(r_start), _ptr(r_len), _ptr(r_val), stream())
+    offs, n, r_start, r_len, r_val = row_runs(vol)
     offs_h = offs.cpu().numpy().astype(np.int64)
     st = r_start[:n].cpu().numpy().astype(np.int64)          # y * Xl + x inside plane z
     ln = r_len[:n].cpu().numpy().astype(np.int64)

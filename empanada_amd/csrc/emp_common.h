@@ -29,9 +29,19 @@ extern thread_local char emp_err_buf[512];
             EMP_FAIL(EMP_ELAUNCH, "%s: launch failed: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
+// Launch `kernel` and check the launch under the kernel's own name; returns from the calling function on failure.
+// A template kernel goes in parentheses: EMP_LAUNCH((k<4, true>), ...).
+#define EMP_LAUNCH(kernel, grid, block, stream, ...)                                      \
+    do {                                                                                  \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__);      \
+        EMP_CHECK_LAUNCH(#kernel);                                                        \
+    } while (0)
+
 static inline hipStream_t emp_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int64_t emp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+static inline int64_t emp_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 // Memory-bound grids: cap at 256 CUs x 8 blocks and grid-stride the rest.
 static inline int emp_grid(int64_t work_items, int block, int max_blocks = 2048)
@@ -40,4 +50,47 @@ static inline int emp_grid(int64_t work_items, int block, int max_blocks = 2048)
     if (g < 1) g = 1;
     if (g > max_blocks) g = max_blocks;
     return (int)g;
+}
+
+// Workspace carver: hands out typed regions of a caller-provided workspace in call order, each starting at the next
+// multiple of `align` bytes, and ends with the total in bytes().  A null base gives null pointers and the same
+// total, so one layout function serves both the emp_*_work_bytes query and the entry point: they cannot disagree.
+struct EmpCarver {
+    char *base;
+    int64_t off = 0;
+    explicit EmpCarver(void *b) : base(reinterpret_cast<char *>(b)) {}
+    template <typename T> T *take(int64_t count, int64_t align = 256)
+    {
+        off = emp_align_up(off, align);
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += count * (int64_t)sizeof(T);
+        return p;
+    }
+    int64_t bytes() const { return off; }
+};
+
+// "Nothing to do": the count is zeroed on the stream and the entry point returns.
+static inline int emp_zero_count(int32_t *n_out, hipStream_t st, const char *msg)
+{
+    if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "%s", msg);
+    return EMP_OK;
+}
+
+// Stream compaction of n items: launch_flags() fills flag[0..n) with 0/1, the scan turns it into output positions
+// pos[0..n] (tmp: emp_scan_tmp_elems(n) elements), launch_emit() writes the flagged items to their positions, and the
+// number of them, pos[n], is copied to *n_out.  The two callables launch one kernel each and return EMP_OK or an
+// error code.
+template <typename Flags, typename Emit>
+static inline int emp_compact(const int32_t *flag, int64_t n, int32_t *pos, int32_t *tmp, int32_t *n_out,
+                              void *stream, const char *copy_msg, Flags launch_flags, Emit launch_emit)
+{
+    int rc = launch_flags();
+    if (rc != EMP_OK) return rc;
+    rc = emp_exclusive_scan_i32(flag, n, pos, tmp, stream);
+    if (rc != EMP_OK) return rc;
+    rc = launch_emit();
+    if (rc != EMP_OK) return rc;
+    if (hipMemcpyAsync(n_out, pos + n, sizeof(int32_t), hipMemcpyDeviceToDevice, emp_stream(stream)) != hipSuccess)
+        EMP_FAIL(EMP_ELAUNCH, "%s", copy_msg);
+    return EMP_OK;
 }

@@ -5,11 +5,6 @@
 #include <hipcub/hipcub.hpp>
 #include <rocprim/rocprim.hpp>
 
-extern "C" int emp_exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out, int32_t *tmp, void *stream);
-extern "C" int64_t emp_scan_tmp_elems(int64_t n);
-
-static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 // ------------------------------------------------------------------------------------------
 // rocPRIM's radix sort takes a merge-sort path for 1024 < n <= 2^20 whose comparison mask is built from
 // T(1) << end_bit: undefined for end_bit == 64, and on the host that builds it the mask comes out as the bits BELOW
@@ -38,7 +33,7 @@ extern "C" int64_t emp_sort_work_bytes(int64_t n)
         sort_pairs(nullptr, bytes_upper, nullptr, nullptr, nullptr, nullptr, (int)n, 1, 64, (hipStream_t)0) != hipSuccess)
         return -1;
     if (bytes_upper > bytes) bytes = bytes_upper;
-    return (int64_t)align_up((int64_t)bytes, 256) + 256;
+    return emp_align_up((int64_t)bytes, 256) + 256;
 }
 
 extern "C" int emp_sort_u64_i32(const uint64_t *keys_in, uint64_t *keys_out, const int32_t *vals_in,
@@ -62,30 +57,32 @@ extern "C" int emp_sort_u64_i32(const uint64_t *keys_in, uint64_t *keys_out, con
 // ------------------------------------------------------------------------------------------
 // C3 voting by coverage count.  Events: (+1 at start, -1 at end), key = group<<41 | pos<<1 | type.
 struct VoteWork {
-    int64_t keys_in, keys_out, vals_in, vals_out, cov, flag_s, flag_e, scan_s, scan_e, scantmp, cub, cub_bytes, total;
+    uint64_t *keys_in, *keys_out;
+    int32_t *vals_in, *vals_out, *cov, *flag_s, *flag_e, *scan_s, *scan_e, *scantmp;
+    char *cub;
+    int64_t cub_bytes, total;
 };
-static VoteWork vote_layout(int64_t n)
+static VoteWork vote_carve(void *work, int64_t n)
 {
-    VoteWork L;
     int64_t m = 2 * (n > 0 ? n : 1);
-    int64_t o = 0;
-    L.keys_in = o; o += align_up(m * 8, 256);
-    L.keys_out = o; o += align_up(m * 8, 256);
-    L.vals_in = o; o += align_up(m * 4, 256);
-    L.vals_out = o; o += align_up(m * 4, 256);
-    L.cov = o; o += align_up((m + 1) * 4, 256);
-    L.flag_s = o; o += align_up(m * 4, 256);
-    L.flag_e = o; o += align_up(m * 4, 256);
-    L.scan_s = o; o += align_up((m + 1) * 4, 256);
-    L.scan_e = o; o += align_up((m + 1) * 4, 256);
-    L.scantmp = o; o += align_up(emp_scan_tmp_elems(m) * 4, 256);
-    L.cub = o;
+    EmpCarver c(work);
+    VoteWork L;
+    L.keys_in = c.take<uint64_t>(m);
+    L.keys_out = c.take<uint64_t>(m);
+    L.vals_in = c.take<int32_t>(m);
+    L.vals_out = c.take<int32_t>(m);
+    L.cov = c.take<int32_t>(m + 1);
+    L.flag_s = c.take<int32_t>(m);
+    L.flag_e = c.take<int32_t>(m);
+    L.scan_s = c.take<int32_t>(m + 1);
+    L.scan_e = c.take<int32_t>(m + 1);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(m));
     L.cub_bytes = emp_sort_work_bytes(m);
-    o += L.cub_bytes;
-    L.total = o;
+    L.cub = c.take<char>(L.cub_bytes);
+    L.total = c.bytes();
     return L;
 }
-extern "C" int64_t emp_vote_work_bytes(int64_t n) { return vote_layout(n).total; }
+extern "C" int64_t emp_vote_work_bytes(int64_t n) { return vote_carve(nullptr, n).total; }
 
 #define VOTE_POS_BITS 40
 #define VOTE_GRP_SHIFT (VOTE_POS_BITS + 1)
@@ -162,38 +159,23 @@ extern "C" int emp_vote_ranges(const int64_t *starts, const int64_t *ends, const
         return EMP_OK;
     }
     EMP_REQUIRE(starts && ends && grp && work && out_ranges, "vote: null pointer");
-    VoteWork L = vote_layout(n);
+    VoteWork L = vote_carve(work, n);
     EMP_REQUIRE(work_bytes >= L.total, "vote: workspace too small");
-    char *w = reinterpret_cast<char *>(work);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(w + L.keys_in);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(w + L.keys_out);
-    int32_t *vals_in = reinterpret_cast<int32_t *>(w + L.vals_in);
-    int32_t *vals_out = reinterpret_cast<int32_t *>(w + L.vals_out);
-    int32_t *cov = reinterpret_cast<int32_t *>(w + L.cov);
-    int32_t *flag_s = reinterpret_cast<int32_t *>(w + L.flag_s);
-    int32_t *flag_e = reinterpret_cast<int32_t *>(w + L.flag_e);
-    int32_t *scan_s = reinterpret_cast<int32_t *>(w + L.scan_s);
-    int32_t *scan_e = reinterpret_cast<int32_t *>(w + L.scan_e);
-    int32_t *scantmp = reinterpret_cast<int32_t *>(w + L.scantmp);
     int64_t m = 2 * n;
     int grid = emp_grid(m, 256, 4096);
-    hipLaunchKernelGGL(vote_events_kernel, dim3(grid), dim3(256), 0, st, starts, ends, grp, n, keys_in, vals_in);
-    EMP_CHECK_LAUNCH("emp_vote_ranges(events)");
-    int rc = emp_sort_u64_i32(keys_in, keys_out, vals_in, vals_out, m, 0, 64, w + L.cub, L.cub_bytes, stream);
+    EMP_LAUNCH(vote_events_kernel, grid, 256, st, starts, ends, grp, n, L.keys_in, L.vals_in);
+    int rc = emp_sort_u64_i32(L.keys_in, L.keys_out, L.vals_in, L.vals_out, m, 0, 64, L.cub, L.cub_bytes, stream);
     if (rc != EMP_OK) return rc;
-    rc = emp_exclusive_scan_i32(vals_out, m, cov, scantmp, stream);
+    rc = emp_exclusive_scan_i32(L.vals_out, m, L.cov, L.scantmp, stream);
     if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(vote_flags_kernel, dim3(grid), dim3(256), 0, st, keys_out, cov, m, vote_thr, flag_s, flag_e);
-    EMP_CHECK_LAUNCH("emp_vote_ranges(flags)");
-    rc = emp_exclusive_scan_i32(flag_s, m, scan_s, scantmp, stream);
+    EMP_LAUNCH(vote_flags_kernel, grid, 256, st, L.keys_out, L.cov, m, vote_thr, L.flag_s, L.flag_e);
+    rc = emp_exclusive_scan_i32(L.flag_s, m, L.scan_s, L.scantmp, stream);
     if (rc != EMP_OK) return rc;
-    rc = emp_exclusive_scan_i32(flag_e, m, scan_e, scantmp, stream);
+    rc = emp_exclusive_scan_i32(L.flag_e, m, L.scan_e, L.scantmp, stream);
     if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(vote_emit_kernel, dim3(grid), dim3(256), 0, st, keys_out, m, flag_s, flag_e, scan_s, scan_e,
-                       out_ranges);
-    hipLaunchKernelGGL(vote_offsets_kernel, dim3((unsigned)emp_cdiv(n_groups + 1, 256)), dim3(256), 0, st, keys_out,
-                       m, scan_s, n_groups, out_off);
-    EMP_CHECK_LAUNCH("emp_vote_ranges");
+    EMP_LAUNCH(vote_emit_kernel, grid, 256, st, L.keys_out, m, L.flag_s, L.flag_e, L.scan_s, L.scan_e, out_ranges);
+    EMP_LAUNCH(vote_offsets_kernel, (unsigned)emp_cdiv(n_groups + 1, 256), 256, st, L.keys_out, m, L.scan_s, n_groups,
+               out_off);
     return EMP_OK;
 }
 
@@ -243,9 +225,8 @@ extern "C" int emp_rle_pair_intersections(const int64_t *starts, const int64_t *
     if (n_pairs == 0) return EMP_OK;
     EMP_REQUIRE(starts && lens && inst_off && pairs && out_inter, "pair_intersections: null pointer");
     int grid = emp_grid(n_pairs, 64, 8192);
-    hipLaunchKernelGGL(pair_intersections_kernel, dim3(grid), dim3(64), 0, emp_stream(stream), starts, lens, inst_off,
-                       pairs, n_pairs, out_inter);
-    EMP_CHECK_LAUNCH("emp_rle_pair_intersections");
+    EMP_LAUNCH(pair_intersections_kernel, grid, 64, emp_stream(stream), starts, lens, inst_off, pairs, n_pairs,
+               out_inter);
     return EMP_OK;
 }
 
@@ -290,9 +271,8 @@ extern "C" int emp_fill_runs_u32(uint32_t *vol, int64_t n_vox, const int64_t *st
     EMP_REQUIRE(vol && starts && lens && order && ids, "fill: null pointer");
     int grid = emp_grid(n_runs * 64, 256, 8192);
     hipStream_t st = emp_stream(stream);
-    hipLaunchKernelGGL(fill_u32_kernel<0>, dim3(grid), dim3(256), 0, st, vol, n_vox, starts, lens, order, n_runs, ids);
-    hipLaunchKernelGGL(fill_u32_kernel<1>, dim3(grid), dim3(256), 0, st, vol, n_vox, starts, lens, order, n_runs, ids);
-    EMP_CHECK_LAUNCH("emp_fill_runs_u32");
+    EMP_LAUNCH(fill_u32_kernel<0>, grid, 256, st, vol, n_vox, starts, lens, order, n_runs, ids);
+    EMP_LAUNCH(fill_u32_kernel<1>, grid, 256, st, vol, n_vox, starts, lens, order, n_runs, ids);
     return EMP_OK;
 }
 
@@ -318,9 +298,7 @@ extern "C" int emp_fill_runs_u8(uint8_t *vol, int64_t n_vox, const int64_t *star
     if (n_runs == 0) return EMP_OK;
     EMP_REQUIRE(vol && starts && lens, "fill_u8: null pointer");
     int grid = emp_grid(n_runs * 64, 256, 8192);
-    hipLaunchKernelGGL(fill_u8_kernel, dim3(grid), dim3(256), 0, emp_stream(stream), vol, n_vox, starts, lens, n_runs,
-                       value);
-    EMP_CHECK_LAUNCH("emp_fill_runs_u8");
+    EMP_LAUNCH(fill_u8_kernel, grid, 256, emp_stream(stream), vol, n_vox, starts, lens, n_runs, value);
     return EMP_OK;
 }
 
@@ -365,9 +343,8 @@ extern "C" int emp_box_pairs(const int32_t *boxes_a, int64_t na, const int32_t *
     EMP_REQUIRE(boxes_a && boxes_b && (out_pairs || cap == 0), "box_pairs: null pointer");
     int64_t blocks = na * emp_cdiv(nb, 256);
     EMP_REQUIRE(blocks < (1LL << 31), "box_pairs: too many boxes (%lld x %lld)", (long long)na, (long long)nb);
-    hipLaunchKernelGGL(box_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, boxes_a, na, boxes_b, nb, ndim,
-                       src_a, src_b, upper_only, out_pairs, cap, n_out);
-    EMP_CHECK_LAUNCH("emp_box_pairs");
+    EMP_LAUNCH(box_pairs_kernel, (unsigned)blocks, 256, st, boxes_a, na, boxes_b, nb, ndim, src_a, src_b, upper_only,
+               out_pairs, cap, n_out);
     return EMP_OK;
 }
 
@@ -403,9 +380,8 @@ extern "C" int emp_fill_table_u32(uint32_t *vol, int64_t HW, int n_slices, int s
     if (n_runs == 0 || n_slices == 0) return EMP_OK;
     EMP_REQUIRE(vol && r_start && r_len && r_comp && c_slice && value, "fill_table: null pointer");
     int grid = emp_grid(n_runs * 64, 256, 8192);
-    hipLaunchKernelGGL(fill_table_kernel, dim3(grid), dim3(256), 0, emp_stream(stream), vol, HW, slice0, r_start, r_len,
-                       r_comp, c_slice, value, n_runs, n_slices);
-    EMP_CHECK_LAUNCH("emp_fill_table_u32");
+    EMP_LAUNCH(fill_table_kernel, grid, 256, emp_stream(stream), vol, HW, slice0, r_start, r_len, r_comp, c_slice, value,
+               n_runs, n_slices);
     return EMP_OK;
 }
 
@@ -442,9 +418,8 @@ extern "C" int emp_scatter_yz_u32(uint32_t *vol, int Z, int Y, int X, const int3
     if (n_runs == 0) return EMP_OK;
     EMP_REQUIRE(vol && r_start && r_len && r_comp && c_slice && value, "scatter_yz: null pointer");
     int grid = emp_grid(n_runs * 64, 256, 8192);
-    hipLaunchKernelGGL(scatter_yz_kernel, dim3(grid), dim3(256), 0, emp_stream(stream), vol, Y, X, r_start, r_len,
-                       r_comp, c_slice, value, n_runs);
-    EMP_CHECK_LAUNCH("emp_scatter_yz_u32");
+    EMP_LAUNCH(scatter_yz_kernel, grid, 256, emp_stream(stream), vol, Y, X, r_start, r_len, r_comp, c_slice, value,
+               n_runs);
     return EMP_OK;
 }
 
@@ -472,9 +447,8 @@ extern "C" int emp_rle_decode(const int64_t *starts, const int64_t *runs, const 
     EMP_REQUIRE(n_runs >= 0, "rle_decode: bad size");
     if (n_runs == 0) return EMP_OK;
     EMP_REQUIRE(starts && runs && offsets && out_indices, "rle_decode: null pointer");
-    hipLaunchKernelGGL(rle_decode_kernel, dim3(emp_grid(n_runs * 64, 256, 8192)), dim3(256), 0, emp_stream(stream),
-                       starts, runs, offsets, n_runs, out_indices);
-    EMP_CHECK_LAUNCH("emp_rle_decode");
+    EMP_LAUNCH(rle_decode_kernel, emp_grid(n_runs * 64, 256, 8192), 256, emp_stream(stream), starts, runs, offsets,
+               n_runs, out_indices);
     return EMP_OK;
 }
 
@@ -503,22 +477,20 @@ extern "C" int emp_rle_encode(const int64_t *indices, int64_t n, int32_t *work, 
 {
     EMP_REQUIRE(n >= 0 && n < (1LL << 31) && n_runs_out, "rle_encode: bad arguments");
     hipStream_t st = emp_stream(stream);
-    if (n == 0) {
-        if (hipMemsetAsync(n_runs_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "rle_encode: memset");
-        return EMP_OK;
-    }
+    if (n == 0) return emp_zero_count(n_runs_out, st, "rle_encode: memset");
     EMP_REQUIRE(indices && work && out_starts && out_runs, "rle_encode: null pointer");
     int32_t *flags = work, *scan = work + n, *tmp = work + 2 * n + 1;
     int grid = emp_grid(n, 256, 4096);
-    hipLaunchKernelGGL(rle_encode_flags_kernel, dim3(grid), dim3(256), 0, st, indices, n, flags);
-    int rc = emp_exclusive_scan_i32(flags, n, scan, tmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(rle_encode_emit_kernel, dim3(grid), dim3(256), 0, st, indices, n, flags, scan, out_starts,
-                       out_runs);
-    if (hipMemcpyAsync(n_runs_out, scan + n, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "rle_encode: copy");
-    EMP_CHECK_LAUNCH("emp_rle_encode");
-    return EMP_OK;
+    return emp_compact(
+        flags, n, scan, tmp, n_runs_out, stream, "rle_encode: copy",
+        [&]() -> int {
+            EMP_LAUNCH(rle_encode_flags_kernel, grid, 256, st, indices, n, flags);
+            return EMP_OK;
+        },
+        [&]() -> int {
+            EMP_LAUNCH(rle_encode_emit_kernel, grid, 256, st, indices, n, flags, scan, out_starts, out_runs);
+            return EMP_OK;
+        });
 }
 
 extern "C" int64_t emp_rle_encode_work_elems(int64_t n) { return 2 * n + 1 + emp_scan_tmp_elems(n > 0 ? n : 1); }

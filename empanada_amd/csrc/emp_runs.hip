@@ -97,10 +97,9 @@ extern "C" int emp_exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out
         return EMP_OK;
     }
     int64_t nb = emp_cdiv(n, SC_B);
-    hipLaunchKernelGGL(scan_block_sums, dim3((unsigned)nb), dim3(SC_T), 0, st, in, n, tmp);
-    hipLaunchKernelGGL(scan_sums, dim3(1), dim3(SC_T), 0, st, tmp, nb, out + n);
-    hipLaunchKernelGGL(scan_apply, dim3((unsigned)nb), dim3(SC_T), 0, st, in, n, tmp, out);
-    EMP_CHECK_LAUNCH("emp_exclusive_scan_i32");
+    EMP_LAUNCH(scan_block_sums, (unsigned)nb, SC_T, st, in, n, tmp);
+    EMP_LAUNCH(scan_sums, 1, SC_T, st, tmp, nb, out + n);
+    EMP_LAUNCH(scan_apply, (unsigned)nb, SC_T, st, in, n, tmp, out);
     return EMP_OK;
 }
 
@@ -223,12 +222,11 @@ extern "C" int emp_runs_count(const uint32_t *pan, int D, int H, int W, int32_t 
     int grid = emp_grid(n_rows * 64, 256, 16384);
     hipStream_t st = emp_stream(stream);
     if (vec4_ok(pan, W))
-        hipLaunchKernelGGL((row_runs_kernel<4, false>), dim3(grid), dim3(256), 0, st, pan, n_rows, W, row_counts,
-                           (const int32_t *)nullptr, H, (int32_t *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr);
+        EMP_LAUNCH((row_runs_kernel<4, false>), grid, 256, st, pan, n_rows, W, row_counts, (const int32_t *)nullptr, H,
+                   (int32_t *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr);
     else
-        hipLaunchKernelGGL((row_runs_kernel<1, false>), dim3(grid), dim3(256), 0, st, pan, n_rows, W, row_counts,
-                           (const int32_t *)nullptr, H, (int32_t *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr);
-    EMP_CHECK_LAUNCH("emp_runs_count");
+        EMP_LAUNCH((row_runs_kernel<1, false>), grid, 256, st, pan, n_rows, W, row_counts, (const int32_t *)nullptr, H,
+                   (int32_t *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr);
     return EMP_OK;
 }
 
@@ -242,40 +240,45 @@ extern "C" int emp_runs_extract(const uint32_t *pan, int D, int H, int W, const 
     int grid = emp_grid(n_rows * 64, 256, 16384);
     hipStream_t st = emp_stream(stream);
     if (vec4_ok(pan, W))
-        hipLaunchKernelGGL((row_runs_kernel<4, true>), dim3(grid), dim3(256), 0, st, pan, n_rows, W,
-                           (int32_t *)nullptr, row_offsets, H, r_start, r_len, r_val);
+        EMP_LAUNCH((row_runs_kernel<4, true>), grid, 256, st, pan, n_rows, W, (int32_t *)nullptr, row_offsets, H, r_start,
+                   r_len, r_val);
     else
-        hipLaunchKernelGGL((row_runs_kernel<1, true>), dim3(grid), dim3(256), 0, st, pan, n_rows, W,
-                           (int32_t *)nullptr, row_offsets, H, r_start, r_len, r_val);
-    EMP_CHECK_LAUNCH("emp_runs_extract");
-    hipLaunchKernelGGL(runs_fix_len, dim3(1024), dim3(256), 0, st, r_start, r_len, row_offsets + n_rows);
-    EMP_CHECK_LAUNCH("emp_runs_extract(fix)");
+        EMP_LAUNCH((row_runs_kernel<1, true>), grid, 256, st, pan, n_rows, W, (int32_t *)nullptr, row_offsets, H, r_start,
+                   r_len, r_val);
+    EMP_LAUNCH(runs_fix_len, 1024, 256, st, r_start, r_len, row_offsets + n_rows);
     return EMP_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // Union-find over runs.
 struct LabelWork {
-    int64_t parent, row, flag, scan, scantmp, hkeys, hvals, total, hsize;
+    int32_t *parent, *row, *flag, *scan, *scantmp;
+    unsigned long long *hkeys;   // open-addressing table of hsize slots for the non-CC classes
+    int32_t *hvals;
+    int64_t hsize, total;        // total in int32 elements
 };
-static inline LabelWork label_layout(int64_t n)
+// the workspace is an int32 array: regions are packed, and only the 64-bit keys need their own (8-byte) alignment
+static LabelWork label_carve(int32_t *work, int64_t n)
 {
-    LabelWork L;
     int64_t T = 64;
     while (T < 2 * n) T <<= 1;
+    EmpCarver c(work);
+    LabelWork L;
     L.hsize = T;
-    L.parent = 0;
-    L.row = L.parent + n;
-    L.flag = L.row + n;
-    L.scan = L.flag + n;
-    L.scantmp = L.scan + n + 1;
-    L.hkeys = L.scantmp + emp_scan_tmp_elems(n);
-    L.hkeys += (L.hkeys & 1);  // 8-byte alignment for the 64-bit keys
-    L.hvals = L.hkeys + 2 * T;
-    L.total = L.hvals + T;
+    L.parent = c.take<int32_t>(n, 4);
+    L.row = c.take<int32_t>(n, 4);
+    L.flag = c.take<int32_t>(n, 4);
+    L.scan = c.take<int32_t>(n + 1, 4);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(n), 4);
+    L.hkeys = c.take<unsigned long long>(T, 8);
+    L.hvals = c.take<int32_t>(T, 4);
+    L.total = c.bytes() / 4;
     return L;
 }
-extern "C" int64_t emp_runs_label_work_elems(int64_t n_runs) { return label_layout(n_runs > 0 ? n_runs : 1).total; }
+extern "C" int64_t emp_runs_label_work_elems(int64_t n_runs)
+{
+    return label_carve(nullptr, n_runs > 0 ? n_runs : 1).total;
+}
 
 __device__ __forceinline__ int uf_find(const int32_t *parent, int a)
 {
@@ -453,44 +456,34 @@ extern "C" int emp_runs_label(const int32_t *r_start, const int32_t *r_len, cons
     EMP_REQUIRE(n_runs >= 0 && n_runs < (1LL << 31), "runs_label: bad n_runs");
     EMP_REQUIRE(label_divisor > 0 && D >= 0 && H > 0 && W > 0, "runs_label: bad arguments");
     hipStream_t st = emp_stream(stream);
-    if (n_runs == 0) {
-        if (hipMemsetAsync(n_comp_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "runs_label: memset");
-        return EMP_OK;
-    }
+    if (n_runs == 0) return emp_zero_count(n_comp_out, st, "runs_label: memset");
     EMP_REQUIRE(r_start && r_len && r_val && r_comp && c_slice && c_label && c_area && c_box && c_first,
                 "runs_label: null pointer");
-    LabelWork L = label_layout(n_runs);
-    int32_t *parent = work + L.parent, *row = work + L.row, *flag = work + L.flag, *scan = work + L.scan;
-    int32_t *scantmp = work + L.scantmp, *hvals = work + L.hvals;
-    unsigned long long *hkeys = reinterpret_cast<unsigned long long *>(work + L.hkeys);
+    LabelWork L = label_carve(work, n_runs);
     int64_t n_rows = (int64_t)D * H;
     int grid = emp_grid(n_runs, 256, 4096);
-    hipLaunchKernelGGL(label_init_kernel, dim3(grid), dim3(256), 0, st, n_runs, n_rows, row_offsets, parent, row);
+    EMP_LAUNCH(label_init_kernel, grid, 256, st, n_runs, n_rows, row_offsets, L.parent, L.row);
     // classes beyond bit 31 and classes whose bit is clear are "plain" (grouped by value): the grouping pass can be
     // left out only when every bit is set AND no uint32 value has a class of 32 or more
     const bool any_plain = (cc_mask != 0xffffffffu) || (0xffffffffLL / label_divisor >= 32);
     if (any_plain) {
-        if (hipMemsetAsync(hkeys, 0, sizeof(unsigned long long) * L.hsize, st) != hipSuccess ||
-            hipMemsetAsync(hvals, 0x7f, sizeof(int32_t) * L.hsize, st) != hipSuccess)
+        if (hipMemsetAsync(L.hkeys, 0, sizeof(unsigned long long) * L.hsize, st) != hipSuccess ||
+            hipMemsetAsync(L.hvals, 0x7f, sizeof(int32_t) * L.hsize, st) != hipSuccess)
             EMP_FAIL(EMP_ELAUNCH, "runs_label: memset");
-        hipLaunchKernelGGL(label_hash_kernel, dim3(grid), dim3(256), 0, st, n_runs, H, label_divisor, cc_mask,
-                           r_val, row, hkeys, hvals, L.hsize, 0, parent);
-        hipLaunchKernelGGL(label_hash_kernel, dim3(grid), dim3(256), 0, st, n_runs, H, label_divisor, cc_mask,
-                           r_val, row, hkeys, hvals, L.hsize, 1, parent);
+        for (int pass = 0; pass < 2; ++pass)
+            EMP_LAUNCH(label_hash_kernel, grid, 256, st, n_runs, H, label_divisor, cc_mask, r_val, L.row, L.hkeys,
+                       L.hvals, L.hsize, pass, L.parent);
     }
-    hipLaunchKernelGGL(label_union_kernel, dim3(grid), dim3(256), 0, st, n_runs, H, W, label_divisor, cc_mask,
-                       r_start, r_len, r_val, row, row_offsets, parent);
-    hipLaunchKernelGGL(label_flatten_kernel, dim3(grid), dim3(256), 0, st, n_runs, parent, flag);
-    EMP_CHECK_LAUNCH("emp_runs_label(union)");
-    int rc = emp_exclusive_scan_i32(flag, n_runs, scan, scantmp, stream);
+    EMP_LAUNCH(label_union_kernel, grid, 256, st, n_runs, H, W, label_divisor, cc_mask, r_start, r_len, r_val, L.row,
+               row_offsets, L.parent);
+    EMP_LAUNCH(label_flatten_kernel, grid, 256, st, n_runs, L.parent, L.flag);
+    int rc = emp_exclusive_scan_i32(L.flag, n_runs, L.scan, L.scantmp, stream);
     if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(label_comp_kernel, dim3(grid), dim3(256), 0, st, n_runs, H, parent, flag, scan, row, r_val,
-                       r_comp, c_slice, c_label, c_area, c_box, c_first, n_comp_out);
-    hipLaunchKernelGGL(label_rank_kernel, dim3((unsigned)emp_cdiv(D, 64)), dim3(64), 0, st, D, label_divisor,
-                       cc_mask, n_comp_out, c_slice, c_label);
-    hipLaunchKernelGGL(label_stats_kernel, dim3(grid), dim3(256), 0, st, n_runs, H, W, r_start, r_len, r_comp,
-                       c_area, c_box);
-    EMP_CHECK_LAUNCH("emp_runs_label");
+    EMP_LAUNCH(label_comp_kernel, grid, 256, st, n_runs, H, L.parent, L.flag, L.scan, L.row, r_val, r_comp, c_slice,
+               c_label, c_area, c_box, c_first, n_comp_out);
+    EMP_LAUNCH(label_rank_kernel, (unsigned)emp_cdiv(D, 64), 64, st, D, label_divisor, cc_mask, n_comp_out, c_slice,
+               c_label);
+    EMP_LAUNCH(label_stats_kernel, grid, 256, st, n_runs, H, W, r_start, r_len, r_comp, c_area, c_box);
     return EMP_OK;
 }
 
@@ -554,8 +547,7 @@ extern "C" int emp_runs_overlap_next(const int32_t *r_start, const int32_t *r_le
     EMP_REQUIRE(r_start && r_len && r_comp && r_val && (out_triplets || cap_triplets == 0),
                 "overlap_next: null pointer");
     int grid = emp_grid(n_runs, 256, 4096);
-    hipLaunchKernelGGL(overlap_next_kernel, dim3(grid), dim3(256), 0, st, n_runs, D, H, W, label_divisor, r_start,
-                       r_len, r_comp, r_val, row_offsets, out_triplets, cap_triplets, n_out);
-    EMP_CHECK_LAUNCH("emp_runs_overlap_next");
+    EMP_LAUNCH(overlap_next_kernel, grid, 256, st, n_runs, D, H, W, label_divisor, r_start, r_len, r_comp, r_val,
+               row_offsets, out_triplets, cap_triplets, n_out);
     return EMP_OK;
 }

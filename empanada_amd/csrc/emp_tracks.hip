@@ -6,17 +6,8 @@
 // 2^40 voxels (cfg 5 has 2^32), 24 bits of instance 16.7 M instances per plane set.
 #include "emp_common.h"
 
-extern "C" int emp_exclusive_scan_i32(const int32_t *in, int64_t n, int32_t *out, int32_t *tmp, void *stream);
-extern "C" int64_t emp_scan_tmp_elems(int64_t n);
-extern "C" int64_t emp_sort_work_bytes(int64_t n);
-extern "C" int emp_sort_u64_i32(const uint64_t *keys_in, uint64_t *keys_out, const int32_t *vals_in,
-                                int32_t *vals_out, int64_t n, int begin_bit, int end_bit, void *work,
-                                int64_t work_bytes, void *stream);
-
 #define TRK_POS_BITS 40
 #define TRK_POS_MASK ((1ULL << TRK_POS_BITS) - 1ULL)
-
-static inline int64_t trk_align(int64_t x) { return (x + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------------------------------ xy / xz lift
 // Run i continues run i-1 (same instance, same slice, flat 2D indices contiguous) exactly when rle_encode over the
@@ -72,6 +63,28 @@ extern "C" int64_t emp_track_work_elems(int64_t n_runs)
     return 2 * n + 2 + emp_scan_tmp_elems(n);
 }
 
+// heads -> scan -> emit over a run table, shared by emp_track_lift (axis 0 / 1) and emp_tile_lift (axis 2)
+static int trk_lift(int axis, const int32_t *r_start, const int32_t *r_len, const int32_t *r_comp,
+                    const int32_t *c_slice, const int32_t *comp_inst, int64_t n_runs, int W, int64_t YX, int X,
+                    int slice0, int64_t inst_base, int64_t origin, int32_t *work, uint64_t *out_key,
+                    int64_t *out_len, int32_t *n_out, void *stream, const char *copy_msg)
+{
+    hipStream_t st = emp_stream(stream);
+    int32_t *head = work, *pos = work + n_runs, *tmp = work + 2 * n_runs + 2;
+    int grid = emp_grid(n_runs, 256, 4096);
+    return emp_compact(
+        head, n_runs, pos, tmp, n_out, stream, copy_msg,
+        [&]() -> int {
+            EMP_LAUNCH(trk_heads_kernel, grid, 256, st, r_start, r_len, r_comp, c_slice, comp_inst, n_runs, head);
+            return EMP_OK;
+        },
+        [&]() -> int {
+            EMP_LAUNCH(trk_emit_kernel, grid, 256, st, axis, r_start, r_len, r_comp, c_slice, comp_inst, n_runs, W, YX,
+                       X, slice0, inst_base, origin, head, pos, out_key, out_len);
+            return EMP_OK;
+        });
+}
+
 extern "C" int emp_track_lift(int axis, const int32_t *r_start, const int32_t *r_len, const int32_t *r_comp,
                               const int32_t *c_slice, const int32_t *comp_inst, int64_t n_runs, int H, int W, int Y,
                               int X, int slice0, int64_t inst_base, int32_t *work, uint64_t *out_key,
@@ -81,27 +94,11 @@ extern "C" int emp_track_lift(int axis, const int32_t *r_start, const int32_t *r
     EMP_REQUIRE(n_runs >= 0 && n_runs < (1LL << 31) && H > 0 && W > 0 && Y > 0 && X > 0 && slice0 >= 0 && n_out,
                 "track_lift: bad sizes");
     EMP_REQUIRE(axis == 0 ? (H == Y && W == X) : (W == X), "track_lift: plane shape does not match the volume");
-    hipStream_t st = emp_stream(stream);
-    if (n_runs == 0) {
-        if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "track_lift: memset");
-        return EMP_OK;
-    }
+    if (n_runs == 0) return emp_zero_count(n_out, emp_stream(stream), "track_lift: memset");
     EMP_REQUIRE(r_start && r_len && r_comp && c_slice && comp_inst && work && out_key && out_len,
                 "track_lift: null pointer");
-    int32_t *head = work, *pos = work + n_runs, *tmp = work + 2 * n_runs + 2;
-    int grid = emp_grid(n_runs, 256, 4096);
-    hipLaunchKernelGGL(trk_heads_kernel, dim3(grid), dim3(256), 0, st, r_start, r_len, r_comp, c_slice, comp_inst,
-                       n_runs, head);
-    EMP_CHECK_LAUNCH("emp_track_lift(heads)");
-    int rc = emp_exclusive_scan_i32(head, n_runs, pos, tmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trk_emit_kernel, dim3(grid), dim3(256), 0, st, axis, r_start, r_len, r_comp, c_slice,
-                       comp_inst, n_runs, W, (int64_t)Y * X, X, slice0, inst_base, (int64_t)0, head, pos, out_key,
-                       out_len);
-    EMP_CHECK_LAUNCH("emp_track_lift(emit)");
-    if (hipMemcpyAsync(n_out, pos + n_runs, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "track_lift: count copy");
-    return EMP_OK;
+    return trk_lift(axis, r_start, r_len, r_comp, c_slice, comp_inst, n_runs, W, (int64_t)Y * X, X, slice0, inst_base,
+                    0, work, out_key, out_len, n_out, stream, "track_lift: count copy");
 }
 
 // ------------------------------------------------------------------------------------------ tile lift (C5)
@@ -118,26 +115,11 @@ extern "C" int emp_tile_lift(const int32_t *r_start, const int32_t *r_len, const
 {
     EMP_REQUIRE(n_runs >= 0 && n_runs < (1LL << 31) && tw > 0 && X >= tw && y0 >= 0 && x0 >= 0 && x0 + tw <= X && n_out,
                 "tile_lift: bad sizes");
-    hipStream_t st = emp_stream(stream);
-    if (n_runs == 0) {
-        if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "tile_lift: memset");
-        return EMP_OK;
-    }
+    if (n_runs == 0) return emp_zero_count(n_out, emp_stream(stream), "tile_lift: memset");
     EMP_REQUIRE(r_start && r_len && r_comp && c_slice && comp_inst && work && out_key && out_len,
                 "tile_lift: null pointer");
-    int32_t *head = work, *pos = work + n_runs, *tmp = work + 2 * n_runs + 2;
-    int grid = emp_grid(n_runs, 256, 4096);
-    hipLaunchKernelGGL(trk_heads_kernel, dim3(grid), dim3(256), 0, st, r_start, r_len, r_comp, c_slice, comp_inst,
-                       n_runs, head);
-    EMP_CHECK_LAUNCH("emp_tile_lift(heads)");
-    int rc = emp_exclusive_scan_i32(head, n_runs, pos, tmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trk_emit_kernel, dim3(grid), dim3(256), 0, st, 2, r_start, r_len, r_comp, c_slice, comp_inst,
-                       n_runs, tw, (int64_t)0, X, 0, inst_base, (int64_t)y0 * X + x0, head, pos, out_key, out_len);
-    EMP_CHECK_LAUNCH("emp_tile_lift(emit)");
-    if (hipMemcpyAsync(n_out, pos + n_runs, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "tile_lift: count copy");
-    return EMP_OK;
+    return trk_lift(2, r_start, r_len, r_comp, c_slice, comp_inst, n_runs, tw, 0, X, 0, inst_base,
+                    (int64_t)y0 * X + x0, work, out_key, out_len, n_out, stream, "tile_lift: count copy");
 }
 
 // ------------------------------------------------------------------------------------------ yz lift
@@ -168,35 +150,39 @@ extern "C" int emp_track_lift_yz(const int32_t *row_offsets, const int32_t *r_st
     EMP_REQUIRE(n_runs >= 0 && n_rows > 0 && Xl > 0 && X >= Xl && x0 >= 0 && x0 + Xl <= X, "track_lift_yz: bad sizes");
     if (n_runs == 0) return EMP_OK;
     EMP_REQUIRE(row_offsets && r_start && r_len && r_val && out_key && out_len, "track_lift_yz: null pointer");
-    hipLaunchKernelGGL(trk_yz_kernel, dim3(emp_grid(n_runs, 256, 4096)), dim3(256), 0, emp_stream(stream),
-                       row_offsets, r_start, r_len, r_val, n_rows, n_runs, Xl, X, x0, inst_base, out_key, out_len);
-    EMP_CHECK_LAUNCH("emp_track_lift_yz");
+    EMP_LAUNCH(trk_yz_kernel, emp_grid(n_runs, 256, 4096), 256, emp_stream(stream), row_offsets, r_start, r_len, r_val,
+               n_rows, n_runs, Xl, X, x0, inst_base, out_key, out_len);
     return EMP_OK;
 }
 
 // ------------------------------------------------------------------------------------------ sort (+ merge)
 struct TrkSortWork {
-    int64_t keys, idx_in, idx_out, len, flag, pos, scantmp, cub, cub_bytes, total;
+    uint64_t *keys;
+    int32_t *idx_in, *idx_out;
+    int64_t *len;
+    int32_t *flag, *pos, *scantmp;
+    char *cub;
+    int64_t cub_bytes, total;
 };
-static TrkSortWork trk_sort_layout(int64_t n)
+// work == nullptr: only .total (and .cub_bytes) mean anything -- the size query
+static TrkSortWork trk_sort_carve(void *work, int64_t n)
 {
-    TrkSortWork L;
     if (n < 1) n = 1;
-    int64_t o = 0;
-    L.keys = o; o += trk_align(n * 8);
-    L.idx_in = o; o += trk_align(n * 4);
-    L.idx_out = o; o += trk_align(n * 4);
-    L.len = o; o += trk_align(n * 8);
-    L.flag = o; o += trk_align(n * 4);
-    L.pos = o; o += trk_align((n + 1) * 4);
-    L.scantmp = o; o += trk_align(emp_scan_tmp_elems(n) * 4);
-    L.cub = o;
+    EmpCarver c(work);
+    TrkSortWork L;
+    L.keys = c.take<uint64_t>(n);
+    L.idx_in = c.take<int32_t>(n);
+    L.idx_out = c.take<int32_t>(n);
+    L.len = c.take<int64_t>(n);
+    L.flag = c.take<int32_t>(n);
+    L.pos = c.take<int32_t>(n + 1);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(n));
     L.cub_bytes = emp_sort_work_bytes(n);
-    o += L.cub_bytes;
-    L.total = o;
+    L.cub = c.take<char>(L.cub_bytes);
+    L.total = c.bytes();
     return L;
 }
-extern "C" int64_t emp_track_sort_work_bytes(int64_t n) { return trk_sort_layout(n).total; }
+extern "C" int64_t emp_track_sort_work_bytes(int64_t n) { return trk_sort_carve(nullptr, n).total; }
 
 __global__ void trk_set_kernel(int32_t *p, int32_t v) { *p = v; }
 
@@ -249,45 +235,31 @@ extern "C" int emp_track_sort(const uint64_t *key_in, const int64_t *len_in, int
 {
     EMP_REQUIRE(n >= 0 && n < (1LL << 31) && n_out, "track_sort: bad arguments");
     hipStream_t st = emp_stream(stream);
-    if (n == 0) {
-        if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "track_sort: memset");
-        return EMP_OK;
-    }
+    if (n == 0) return emp_zero_count(n_out, st, "track_sort: memset");
     EMP_REQUIRE(key_in && len_in && work && out_len, "track_sort: null pointer");
-    TrkSortWork L = trk_sort_layout(n);
+    TrkSortWork L = trk_sort_carve(work, n);
     EMP_REQUIRE(work_bytes >= L.total, "track_sort: workspace too small");
-    char *w = reinterpret_cast<char *>(work);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(w + L.keys);
-    int32_t *idx_in = reinterpret_cast<int32_t *>(w + L.idx_in);
-    int32_t *idx_out = reinterpret_cast<int32_t *>(w + L.idx_out);
-    int64_t *len = reinterpret_cast<int64_t *>(w + L.len);
-    int32_t *flag = reinterpret_cast<int32_t *>(w + L.flag);
-    int32_t *pos = reinterpret_cast<int32_t *>(w + L.pos);
-    int32_t *scantmp = reinterpret_cast<int32_t *>(w + L.scantmp);
     int grid = emp_grid(n, 256, 4096);
-    hipLaunchKernelGGL(trk_iota_kernel, dim3(grid), dim3(256), 0, st, idx_in, n);
-    int rc = emp_sort_u64_i32(key_in, keys, idx_in, idx_out, n, 0, 64, w + L.cub, L.cub_bytes, stream);
+    EMP_LAUNCH(trk_iota_kernel, grid, 256, st, L.idx_in, n);
+    int rc = emp_sort_u64_i32(key_in, L.keys, L.idx_in, L.idx_out, n, 0, 64, L.cub, L.cub_bytes, stream);
     if (rc != EMP_OK) return rc;
     if (!merge_touching) {
-        hipLaunchKernelGGL(trk_gather_kernel, dim3(grid), dim3(256), 0, st, keys, idx_out, len_in, n, out_key, out_st,
-                           out_len);
-        EMP_CHECK_LAUNCH("emp_track_sort(gather)");
-        hipLaunchKernelGGL(trk_set_kernel, dim3(1), dim3(1), 0, st, n_out, (int32_t)n);
-        EMP_CHECK_LAUNCH("emp_track_sort(count)");
+        EMP_LAUNCH(trk_gather_kernel, grid, 256, st, L.keys, L.idx_out, len_in, n, out_key, out_st, out_len);
+        EMP_LAUNCH(trk_set_kernel, 1, 1, st, n_out, (int32_t)n);
         return EMP_OK;
     }
-    hipLaunchKernelGGL(trk_gather_kernel, dim3(grid), dim3(256), 0, st, keys, idx_out, len_in, n,
-                       (uint64_t *)nullptr, (int64_t *)nullptr, len);
-    hipLaunchKernelGGL(trk_touch_heads_kernel, dim3(grid), dim3(256), 0, st, keys, len, n, flag);
-    EMP_CHECK_LAUNCH("emp_track_sort(heads)");
-    rc = emp_exclusive_scan_i32(flag, n, pos, scantmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trk_touch_emit_kernel, dim3(grid), dim3(256), 0, st, keys, len, n, flag, pos, out_key, out_st,
-                       out_len);
-    EMP_CHECK_LAUNCH("emp_track_sort(emit)");
-    if (hipMemcpyAsync(n_out, pos + n, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "track_sort: count copy");
-    return EMP_OK;
+    EMP_LAUNCH(trk_gather_kernel, grid, 256, st, L.keys, L.idx_out, len_in, n, (uint64_t *)nullptr, (int64_t *)nullptr,
+               L.len);
+    return emp_compact(
+        L.flag, n, L.pos, L.scantmp, n_out, stream, "track_sort: count copy",
+        [&]() -> int {
+            EMP_LAUNCH(trk_touch_heads_kernel, grid, 256, st, L.keys, L.len, n, L.flag);
+            return EMP_OK;
+        },
+        [&]() -> int {
+            EMP_LAUNCH(trk_touch_emit_kernel, grid, 256, st, L.keys, L.len, n, L.flag, L.pos, out_key, out_st, out_len);
+            return EMP_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------ small table kernels
@@ -311,9 +283,8 @@ extern "C" int emp_track_offsets(const uint64_t *keys_sorted, int64_t n, int64_t
 {
     EMP_REQUIRE(n >= 0 && n_inst >= 0 && n_inst < (1LL << 24) && out_off, "track_offsets: bad arguments");
     EMP_REQUIRE(n == 0 || keys_sorted, "track_offsets: null keys");
-    hipLaunchKernelGGL(trk_offsets_kernel, dim3((unsigned)emp_cdiv(n_inst + 1, 256)), dim3(256), 0,
-                       emp_stream(stream), keys_sorted, n, n_inst, out_off);
-    EMP_CHECK_LAUNCH("emp_track_offsets");
+    EMP_LAUNCH(trk_offsets_kernel, (unsigned)emp_cdiv(n_inst + 1, 256), 256, emp_stream(stream), keys_sorted, n, n_inst,
+               out_off);
     return EMP_OK;
 }
 
@@ -337,9 +308,7 @@ extern "C" int emp_track_expand(const int64_t *off, const int32_t *obj_val, int6
     EMP_REQUIRE(n_obj > 0 && n_runs >= 0, "track_expand: bad sizes");
     if (n_runs == 0) return EMP_OK;
     EMP_REQUIRE(off && obj_val && out, "track_expand: null pointer");
-    hipLaunchKernelGGL(trk_expand_kernel, dim3(emp_grid(n_runs, 256, 4096)), dim3(256), 0, emp_stream(stream), off,
-                       obj_val, n_obj, n_runs, out);
-    EMP_CHECK_LAUNCH("emp_track_expand");
+    EMP_LAUNCH(trk_expand_kernel, emp_grid(n_runs, 256, 4096), 256, emp_stream(stream), off, obj_val, n_obj, n_runs, out);
     return EMP_OK;
 }
 
@@ -374,23 +343,20 @@ extern "C" int emp_track_clip(const uint64_t *key, const int64_t *len, int64_t n
 {
     EMP_REQUIRE(n >= 0 && n < (1LL << 31) && lo >= 0 && hi >= lo && n_out, "track_clip: bad arguments");
     hipStream_t st = emp_stream(stream);
-    if (n == 0) {
-        if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "track_clip: memset");
-        return EMP_OK;
-    }
+    if (n == 0) return emp_zero_count(n_out, st, "track_clip: memset");
     EMP_REQUIRE(key && len && work && out_key && out_len, "track_clip: null pointer");
     int32_t *keep = work, *pos = work + n, *tmp = work + 2 * n + 2;
     int grid = emp_grid(n, 256, 4096);
-    hipLaunchKernelGGL(trk_clip_flags_kernel, dim3(grid), dim3(256), 0, st, key, len, n, lo, hi, keep);
-    EMP_CHECK_LAUNCH("emp_track_clip(flags)");
-    int rc = emp_exclusive_scan_i32(keep, n, pos, tmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trk_clip_emit_kernel, dim3(grid), dim3(256), 0, st, key, len, n, lo, hi, keep, pos, out_key,
-                       out_len);
-    EMP_CHECK_LAUNCH("emp_track_clip(emit)");
-    if (hipMemcpyAsync(n_out, pos + n, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "track_clip: count copy");
-    return EMP_OK;
+    return emp_compact(
+        keep, n, pos, tmp, n_out, stream, "track_clip: count copy",
+        [&]() -> int {
+            EMP_LAUNCH(trk_clip_flags_kernel, grid, 256, st, key, len, n, lo, hi, keep);
+            return EMP_OK;
+        },
+        [&]() -> int {
+            EMP_LAUNCH(trk_clip_emit_kernel, grid, 256, st, key, len, n, lo, hi, keep, pos, out_key, out_len);
+            return EMP_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------ overlap triplets
@@ -428,59 +394,51 @@ __global__ void trip_emit_kernel(const uint64_t *__restrict__ keys, const int32_
 }
 
 struct TripWork {
-    int64_t keys_in, keys_out, vals_in, vals_out, head, pos, scantmp, cub, cub_bytes, total;
+    uint64_t *keys_in, *keys_out;
+    int32_t *vals_in, *vals_out, *head, *pos, *scantmp;
+    char *cub;
+    int64_t cub_bytes, total;
 };
-static TripWork trip_layout(int64_t n)
+static TripWork trip_carve(void *work, int64_t n)
 {
-    TripWork L;
     if (n < 1) n = 1;
-    int64_t o = 0;
-    L.keys_in = o; o += trk_align(n * 8);
-    L.keys_out = o; o += trk_align(n * 8);
-    L.vals_in = o; o += trk_align(n * 4);
-    L.vals_out = o; o += trk_align(n * 4);
-    L.head = o; o += trk_align(n * 4);
-    L.pos = o; o += trk_align((n + 1) * 4);
-    L.scantmp = o; o += trk_align(emp_scan_tmp_elems(n) * 4);
-    L.cub = o;
+    EmpCarver c(work);
+    TripWork L;
+    L.keys_in = c.take<uint64_t>(n);
+    L.keys_out = c.take<uint64_t>(n);
+    L.vals_in = c.take<int32_t>(n);
+    L.vals_out = c.take<int32_t>(n);
+    L.head = c.take<int32_t>(n);
+    L.pos = c.take<int32_t>(n + 1);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(n));
     L.cub_bytes = emp_sort_work_bytes(n);
-    o += L.cub_bytes;
-    L.total = o;
+    L.cub = c.take<char>(L.cub_bytes);
+    L.total = c.bytes();
     return L;
 }
-extern "C" int64_t emp_triplets_reduce_work_bytes(int64_t n) { return trip_layout(n).total; }
+extern "C" int64_t emp_triplets_reduce_work_bytes(int64_t n) { return trip_carve(nullptr, n).total; }
 
 extern "C" int emp_triplets_reduce(const int32_t *trip, int64_t n, void *work, int64_t work_bytes, int32_t *out,
                                    int32_t *n_out, void *stream)
 {
     EMP_REQUIRE(n >= 0 && n < (1LL << 31) && n_out, "triplets_reduce: bad arguments");
     hipStream_t st = emp_stream(stream);
-    if (n == 0) {
-        if (hipMemsetAsync(n_out, 0, sizeof(int32_t), st) != hipSuccess) EMP_FAIL(EMP_ELAUNCH, "triplets_reduce: memset");
-        return EMP_OK;
-    }
+    if (n == 0) return emp_zero_count(n_out, st, "triplets_reduce: memset");
     EMP_REQUIRE(trip && work && out, "triplets_reduce: null pointer");
-    TripWork L = trip_layout(n);
+    TripWork L = trip_carve(work, n);
     EMP_REQUIRE(work_bytes >= L.total, "triplets_reduce: workspace too small");
-    char *w = reinterpret_cast<char *>(work);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(w + L.keys_in);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(w + L.keys_out);
-    int32_t *vals_in = reinterpret_cast<int32_t *>(w + L.vals_in);
-    int32_t *vals_out = reinterpret_cast<int32_t *>(w + L.vals_out);
-    int32_t *head = reinterpret_cast<int32_t *>(w + L.head);
-    int32_t *pos = reinterpret_cast<int32_t *>(w + L.pos);
-    int32_t *scantmp = reinterpret_cast<int32_t *>(w + L.scantmp);
     int grid = emp_grid(n, 256, 4096);
-    hipLaunchKernelGGL(trip_keys_kernel, dim3(grid), dim3(256), 0, st, trip, n, keys_in, vals_in);
-    EMP_CHECK_LAUNCH("emp_triplets_reduce(keys)");
-    int rc = emp_sort_u64_i32(keys_in, keys_out, vals_in, vals_out, n, 0, 64, w + L.cub, L.cub_bytes, stream);
+    EMP_LAUNCH(trip_keys_kernel, grid, 256, st, trip, n, L.keys_in, L.vals_in);
+    int rc = emp_sort_u64_i32(L.keys_in, L.keys_out, L.vals_in, L.vals_out, n, 0, 64, L.cub, L.cub_bytes, stream);
     if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trip_heads_kernel, dim3(grid), dim3(256), 0, st, keys_out, n, head);
-    rc = emp_exclusive_scan_i32(head, n, pos, scantmp, stream);
-    if (rc != EMP_OK) return rc;
-    hipLaunchKernelGGL(trip_emit_kernel, dim3(grid), dim3(256), 0, st, keys_out, vals_out, n, head, pos, out);
-    EMP_CHECK_LAUNCH("emp_triplets_reduce(emit)");
-    if (hipMemcpyAsync(n_out, pos + n, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        EMP_FAIL(EMP_ELAUNCH, "triplets_reduce: count copy");
-    return EMP_OK;
+    return emp_compact(
+        L.head, n, L.pos, L.scantmp, n_out, stream, "triplets_reduce: count copy",
+        [&]() -> int {
+            EMP_LAUNCH(trip_heads_kernel, grid, 256, st, L.keys_out, n, L.head);
+            return EMP_OK;
+        },
+        [&]() -> int {
+            EMP_LAUNCH(trip_emit_kernel, grid, 256, st, L.keys_out, L.vals_out, n, L.head, L.pos, out);
+            return EMP_OK;
+        });
 }

@@ -183,16 +183,8 @@ def lift_runs(table, comp_inst_local, axis, shape3d, slice0=0, inst_base=0):
         vol = torch.zeros((Z, Y, Xl), dtype=torch.int32, device=dev).view(torch.uint32)
         _hip.call('emp_scatter_yz_u32', _hip._ptr(vol), Z, Y, Xl, _hip._ptr(table.r_start), _hip._ptr(table.r_len),
                   _hip._ptr(table.r_comp), _hip._ptr(table.c_slice), _hip._ptr(value), n_runs, st)
-        rows = torch.empty((Z * Y,), dtype=torch.int32, device=dev)
-        _hip.call('emp_runs_count', _hip._ptr(vol), Z, Y, Xl, _hip._ptr(rows), st)
-        offs = _hip.exclusive_scan_i32(rows)
-        n = int(offs[-1].item())
+        offs, n, r_start, r_len, r_val = _hip.row_runs(vol)
         cap = max(n, 1)
-        r_start = torch.empty((cap,), dtype=torch.int32, device=dev)
-        r_len = torch.empty_like(r_start)
-        r_val = torch.empty((cap,), dtype=torch.uint32, device=dev)
-        _hip.call('emp_runs_extract', _hip._ptr(vol), Z, Y, Xl, _hip._ptr(offs), _hip._ptr(r_start), _hip._ptr(r_len),
-                  _hip._ptr(r_val), st)
         del vol
         key = torch.empty((cap,), dtype=torch.int64, device=dev)
         ln = torch.empty((cap,), dtype=torch.int64, device=dev)

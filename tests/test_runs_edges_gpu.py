@@ -1702,3 +1702,26 @@ def test_track_clip(hip, interval):
     assert m == len(ek) and int(ok[n]) == -7
     np.testing.assert_array_equal(_np_u64(ok[:m]), ek)
     np.testing.assert_array_equal(_np(ol[:m]), el)
+
+
+# n = 0 with null data, work and output pointers: (entry point, arguments; COUNT stands for the count pointer)
+COUNT = object()
+NO_INPUT_CALLS = {
+    'track_lift_xy': ('emp_track_lift', (0, None, None, None, None, None, 0, 5, 7, 5, 7, 0, 0, None, None, None, COUNT)),
+    'track_lift_xz': ('emp_track_lift', (1, None, None, None, None, None, 0, 4, 7, 5, 7, 2, 9, None, None, None, COUNT)),
+    'tile_lift': ('emp_tile_lift', (None, None, None, None, None, 0, 4, 9, 2, 3, 0, None, None, None, COUNT)),
+    'track_clip': ('emp_track_clip', (None, None, 0, 100, 200, None, None, None, COUNT)),
+    'triplets_reduce': ('emp_triplets_reduce', (None, 0, None, 0, None, COUNT)),
+    'rle_encode': ('emp_rle_encode', (None, 0, None, None, None, COUNT)),
+}
+
+
+@pytest.mark.parametrize('name', list(NO_INPUT_CALLS))
+def test_compaction_no_input(hip, name):
+    """the shared early-out of the flags -> scan -> emit entry points: nothing to compact is valid without any data,
+    work or output pointer; the count is zeroed on the stream and nothing next to it is written"""
+    fn, args = NO_INPUT_CALLS[name]
+    cnt = _full(3, torch.int32)                                     # sentinel, count, sentinel
+    ptr = cnt.data_ptr() + 4
+    hip.call(fn, *[ptr if a is COUNT else a for a in args], hip.stream())
+    assert _np(cnt).tolist() == [-7, 0, -7]

@@ -136,3 +136,31 @@ def test_track_references_agree():
     key, ln = E.clip_input()
     for lo, hi in E.CLIP_INTERVALS:
         E.clip_refs(key, ln, lo, hi)
+
+
+WORK_N = [0, 1, 2047, 2048, 2049, 100000]
+# recorded from the library before the layouts were moved onto the shared workspace carver.  The three byte counts
+# are taken without the radix sort's own workspace (it depends on the rocPRIM version, and its query answers -1 where
+# rocPRIM cannot size itself without a device; either way it is added into the total as it is)
+WORK_SIZES = {
+    'emp_scan_tmp_elems': [2, 2, 2, 2, 3, 50],
+    'emp_track_work_elems': [6, 6, 4098, 4100, 4103, 200052],
+    'emp_rle_encode_work_elems': [3, 5, 4097, 4099, 4102, 200051],
+    'emp_runs_label_work_elems': [200, 200, 20480, 20484, 32776, 1186484],
+    'emp_track_sort_work_bytes': [1792, 1792, 65792, 66048, 67328, 3200768],
+    'emp_triplets_reduce_work_bytes': [1792, 1792, 65792, 66048, 67328, 3200768],
+    'emp_vote_work_bytes': [2560, 2560, 180480, 181248, 182784, 8801280],
+}
+
+
+def test_work_sizes_unchanged():
+    """a rewritten layout cannot silently shrink a workspace: every size query answers what it always did"""
+    from empanada_amd import _hip
+    _hip.load()
+    q = _hip.query
+    sort_items = {'emp_track_sort_work_bytes': lambda n: n, 'emp_triplets_reduce_work_bytes': lambda n: n,
+                  'emp_vote_work_bytes': lambda n: 2 * max(n, 1)}
+    for name, want in WORK_SIZES.items():
+        got = [q(name, n) - (q('emp_sort_work_bytes', sort_items[name](n)) if name in sort_items else 0)
+               for n in WORK_N]
+        assert got == want, name
