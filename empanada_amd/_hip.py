@@ -42,6 +42,8 @@ SIGNATURES = {
     'emp_conv_k_slab_cin': (_I, [_L, _I, _I, _I, _I]),
     'emp_conv_k_slab_geom': (_I, [_L, _I, _I, _I, _I, _I, _I, _I, _I]),
     'emp_conv1x1_ws_eligible': (_I, [_L, _I, _I, _I, _I, _I, _I, _I]),
+    'emp_conv1x1_ws_kind_for': (_I, [_L, _I, _I, _I, _I, _I, _I, _I, _I]),
+    'emp_conv1x1_ws_launches': (_L, [_I]),
     'emp_gconv_chunk': (_I, [_I]),
     'emp_gconv3x3_bn_act_nhwc': (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     'emp_conv_bn_act_nhwc': (_I, [_P, _P, _P, _P, _P, _L, _I] + [_I] * 10 + [_P, _L, _P]),

@@ -604,8 +604,9 @@ extern "C" int emp_conv_k_slab_cin(int64_t M, int Cout, int batch, int has_resid
 
 // D4b (emp_conv1x1.hip): the weight-stationary kernel for short-K pointwise layers.  Kind 1 (conv3 / shortcut shapes) sums
 // over 64-channel slabs; kind 2 (256 -> 64, 64 -> 64, 256 -> 128 without a residual) and the batched GEMM sum in the
-// order of the tiled kernel's plan, so emp_conv_k_slab* keep their answers for them.
-extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_kind(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu);
+// order of the tiled kernel's plan, so emp_conv_k_slab* keep their answers for them; so does kind 3 (Cin 256 + residual:
+// layer3's conv3), in the 32-channel slabs of the residual-prefetch plan.
+extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_kind(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int has_residual);
 extern "C" __attribute__((visibility("hidden"))) int emp_conv1x1_ws_launch(int kind, const float *x, const float *w, const float *scale, const float *shift,
                                      const float *res, int64_t res_ps, int relu, int64_t M, int Cin, int Cout,
                                      float *out, int64_t out_ps, void *stream);
@@ -616,7 +617,7 @@ extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_launch(const fl
 extern "C" int emp_conv_k_slab_geom(int64_t M, int Cout, int has_residual, int Cin, int KH, int KW, int stride, int pad,
                                     int relu)
 {
-    if (emp_conv1x1_ws_kind(M, Cin, Cout, KH, KW, stride, pad, relu) == 1) return 64;
+    if (emp_conv1x1_ws_kind(M, Cin, Cout, KH, KW, stride, pad, relu, has_residual) == 1) return 64;
     return cg_plan(M, Cout, 1, has_residual != 0 && relu != 2, true, true, Cin).slab;
 }
 
@@ -650,13 +651,17 @@ extern "C" int emp_conv_bn_act_nhwc(const float *x, const float *w_okkc, const f
     const bool io_vec_ok = res_vec_ok && (out_pixel_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                            (!scale || (reinterpret_cast<uintptr_t>(scale) & 15) == 0) &&
                            (!shift || (reinterpret_cast<uintptr_t>(shift) & 15) == 0);
-    const int ws = io_vec_ok && scale && shift ? emp_conv1x1_ws_kind(g.M, Cin, Cout, KH, KW, stride, pad, relu) : 0;
+    const int ws = io_vec_ok && scale && shift ? emp_conv1x1_ws_kind(g.M, Cin, Cout, KH, KW, stride, pad, relu, residual != nullptr) : 0;
     if (ws == 1)
         return emp_conv1x1_ws_launch(1, x, w_okkc, scale, shift, residual, res_pixel_stride, relu, g.M, Cin, Cout, out,
                                      out_pixel_stride, stream);
     const CgPlan pl = cg_plan(g.M, Cout, 1, residual != nullptr && relu != 2, res_vec_ok, true, Cin);
     if (ws == 2 && !residual && pl.slab == 16)       // same summation order as the tiled kernel below
         return emp_conv1x1_ws_launch(2, x, w_okkc, scale, shift, nullptr, res_pixel_stride, relu, g.M, Cin, Cout, out,
+                                     out_pixel_stride, stream);
+    if (ws == 3 && residual && pl.respf && pl.slab == 32 &&  // likewise: the residual-prefetch plan's 32-channel slabs
+        res_pixel_stride < (1 << 24) && out_pixel_stride < (1 << 24))   // (its lane offsets are 32-bit)
+        return emp_conv1x1_ws_launch(3, x, w_okkc, scale, shift, residual, res_pixel_stride, relu, g.M, Cin, Cout, out,
                                      out_pixel_stride, stream);
     const bool narrow = pl.narrow, respf = pl.respf, bk16 = pl.slab == 16;
     EMP_REQUIRE((int64_t)pl.tiles_m * pl.tiles_n < (1LL << 28), "conv: too many tiles");

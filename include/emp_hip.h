@@ -141,9 +141,25 @@ int emp_conv_k_slab_cin(int64_t M, int Cout, int batch, int has_residual, int Ci
  * batch * M >= 262 144 (the Winograd F(4x4,3x3) GEMMs of layer1 / layer2).  For THESE it sums in the order of the tiled
  * kernel (K-slab emp_conv_k_slab_cin / emp_conv_k_slab, 16 at such sizes), so the result does not depend on which
  * kernel ran and emp_conv_k_slab* answer as before.  emp_conv1x1_ws_eligible: 1 for every convolution geometry the
- * kernel takes (for the conv1 shapes: given no residual); EMP_CONV_NO_WS=1 in the environment turns all of it off. */
+ * kernel takes without a residual (for the conv1 shapes: given no residual); EMP_CONV_NO_WS=1 in the environment turns
+ * all of it off.
+ * Kind 3: 1x1, stride 1, no padding, Cin == 256, Cout a multiple of 128 up to 1024, at least 65 536 output pixels and
+ * at least 8 * 65 536 / (Cout / 128) of them (sixteen 32-pixel tiles for every wave of the persistent grid), WITH
+ * a residual and relu in {0, 1} (layer3's conv3 + identity, 256 -> 1024) also runs on the weight-stationary kernel --
+ * when residual, out, scale and shift are 16-byte aligned, both pixel strides are multiples of 4 below 2^24, and the
+ * tiled kernel's plan for the call is its residual-prefetch variant (K-slab 32).  It sums in THAT order (slabs of 32
+ * channels ascending, inside a slab j = 0..15: channel j, then channel 16 + j), so the result does not depend on which
+ * kernel ran and emp_conv_k_slab_geom keeps answering 32.  Without a residual these shapes stay on the tiled kernel.
+ * emp_conv1x1_ws_kind_for: the kind (0: tiled kernel; 1: the 64-slab shapes; 2: the conv1 shapes; 3) a call of that
+ * geometry with / without a residual takes, given aligned operands.  EMP_CONV_NO_WS3=1 turns kind 3 alone off
+ * (experiments: A/B against the tiled kernel). */
 int emp_conv_k_slab_geom(int64_t M, int Cout, int has_residual, int Cin, int KH, int KW, int stride, int pad, int relu);
 int emp_conv1x1_ws_eligible(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu);
+int emp_conv1x1_ws_kind_for(int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int has_residual);
+/* number of weight-stationary launches emp_conv_bn_act_nhwc has made so far in this process for kind 1, 2 or 3 (-1 for
+ * another kind): the dispatch also depends on alignment, pixel strides and the tiled plan, which the queries above do
+ * not see, so this is how a test tells which kernel a call took. */
+int64_t emp_conv1x1_ws_launches(int kind);
 /* relu == 2 selects the squeeze-excite gate epilogue (SqueezeExcite.forward, empanada/models/blocks.py:35-50:
  * x * sigmoid(conv(s) + bias)): out = residual * (1 / (1 + expf(-(acc * scale + shift)))), residual = the gated
  * tensor x (required); the division and the product are separate fp32 roundings, expf is the device library's;
