@@ -74,6 +74,7 @@ SIGNATURES = {
     'emp_pr_point_sample': (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P]),
     'emp_pr_scatter': (_I, [_P, _I, _P, _I, _I, _I, _L, _P, _P]),
     'emp_median_harden_stack': (_I, [_P, _I, _I, _L, _I, _F, _P, _P, _P]),
+    'emp_median_harden_window': (_I, [_P, _P, _P, _I, _I, _L, _I, _F, _P, _P, _P]),
     'emp_median_step': (_I, [_c.POINTER(_P), _I, _L, _P, _P]),
     'emp_harden': (_I, [_P, _I, _I, _L, _F, _P, _P]),
     'emp_find_centers': (_I, [_P, _I, _I, _I, _F, _I, _I, _P, _P, _P]),
@@ -242,6 +243,45 @@ def _expect(what, t, dtype=None, shape=None, numel=None):
     return t
 
 
+def median_harden_window(prob, ks, thr, hist=None, halo=None, want_tail=False, tail_out=None):
+    """The recursive median + harden of a WINDOW of a longer stack (emp_median_harden_window).
+    prob (D,C,H,W) fp32 cuda: the window's raw probabilities; hist (m,C,H,W), m = ks // 2: the filtered values of the m
+    slices before it (None = the window starts the axis); halo (m,C,H,W): the raw values of the m slices after it (None =
+    it ends the axis).  Returns sem (D,H,W) u8 -- rows of median_harden_stack(cat(hist, prob, halo)) bit for bit, without
+    the concatenation -- and, with want_tail or tail_out, the filtered values of the window's last m slices (the next
+    window's hist), written into tail_out when given; tail_out may be hist itself."""
+    require_gpu()
+    _expect("median_harden_window: prob", prob, torch.float32)
+    if prob.dim() != 4:
+        raise HipError(f"median_harden_window: prob: shape {tuple(prob.shape)}, expected (D, C, H, W)")
+    if isinstance(ks, bool) or int(ks) != ks or not 1 <= int(ks) <= MAX_KS or not int(ks) & 1:
+        raise HipError(f"median_harden_window: ks={ks!r} must be odd in 1..{MAX_KS}")
+    ks = int(ks)
+    D, C, H, W = prob.shape
+    m = ks // 2
+    ends = (('hist', hist), ('halo', halo), ('tail_out', tail_out))
+    for what, t in ends:
+        if t is None:
+            continue
+        if m == 0:
+            raise HipError(f"median_harden_window: ks=1 hardens only, {what} must be None")
+        _expect(f"median_harden_window: {what}", t, torch.float32, (m, C, H, W))
+        if t.device != prob.device:
+            raise HipError(f"median_harden_window: {what} is on {t.device}, prob on {prob.device}")
+    if m == 0 and want_tail:
+        raise HipError("median_harden_window: ks=1 hardens only, there is no tail")
+    for what, t in (('prob', prob),) + ends:
+        if t is not None and not t.is_contiguous():
+            raise HipError(f"median_harden_window: {what} must be contiguous (a copy would be a window-sized allocation)")
+    sem = torch.empty((D, H, W), dtype=torch.uint8, device=prob.device)
+    tail = tail_out
+    if tail is None and want_tail:
+        tail = torch.empty((m, C, H, W), dtype=torch.float32, device=prob.device)
+    call('emp_median_harden_window', _ptr(hist), _ptr(prob), _ptr(halo), D, C, H * W, ks, float(thr), _ptr(sem),
+         _ptr(tail), stream())
+    return (sem, tail) if tail is not None else sem
+
+
 def median_step(slices, out=None):
     """median over a list of ks same-shape fp32 cuda tensors (engines.py:59-66)."""
     require_gpu()
@@ -323,8 +363,9 @@ def group_pixels(idx, cnt, offsets, step, sem=None, thing_list=()):
 
 
 def fuse_panoptic(sem, ids, cap, n_classes, thing_list, label_divisor, stuff_area, void_label, up=1,
-                  out_dtype=torch.uint32):
-    """sem (D,H,W) u8, ids (D,H/up,W/up) u16 -> pan (D,H,W) uint32 or int64."""
+                  out_dtype=torch.uint32, out=None):
+    """sem (D,H,W) u8, ids (D,H/up,W/up) u16 -> pan (D,H,W) uint32 or int64.  out: a contiguous (D,H,W) tensor of
+    out_dtype to write instead of a new one (e.g. slices [lo, hi) of a plane's label tensor)."""
     require_gpu()
     _expect("fuse_panoptic: class map", sem, torch.uint8)
     D, H, W = sem.shape
@@ -337,7 +378,12 @@ def fuse_panoptic(sem, ids, cap, n_classes, thing_list, label_divisor, stuff_are
         mask |= 1 << int(t)
     work = torch.empty((query('emp_fuse_work_elems', D, int(cap), int(n_classes)),), dtype=torch.int32,
                        device=sem.device)
-    pan = torch.empty((D, H, W), dtype=out_dtype, device=sem.device)
+    if out is None:
+        pan = torch.empty((D, H, W), dtype=out_dtype, device=sem.device)
+    else:
+        pan = _expect("fuse_panoptic: out", out, out_dtype, (D, H, W))
+        if not pan.is_contiguous() or pan.device != sem.device:
+            raise HipError("fuse_panoptic: out must be contiguous and on the class map's device")
     p32 = _ptr(pan) if out_dtype == torch.uint32 else None
     p64 = _ptr(pan) if out_dtype == torch.int64 else None
     assert (p32 is None) != (p64 is None), "out_dtype must be torch.uint32 or torch.int64"

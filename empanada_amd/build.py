@@ -24,7 +24,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get('HIPCC', 'hipcc')
-    headers = [os.path.join(CSRC, 'emp_common.h'), os.path.join(CSRC, 'emp_wino4.h'), os.path.join(HERE, '..', 'include', 'emp_hip.h')]
+    headers = [os.path.join(CSRC, 'emp_common.h'), os.path.join(CSRC, 'emp_wino4.h'), os.path.join(CSRC, 'emp_median_kernels.inc'), os.path.join(HERE, '..', 'include', 'emp_hip.h')]
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

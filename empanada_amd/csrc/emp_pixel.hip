@@ -37,200 +37,59 @@ __device__ __forceinline__ float median_regs(const float (&in)[KS])
 }
 
 // ------------------------------------------------------------------------------------------
-// P1+P2, C == 1: one thread per pixel walks the stack in z with the filter window in registers.
-// Loads of the next PF slices are issued before the current PF medians are computed so that
-// every lane keeps PF dword loads in flight (the recursion itself is serial in z).
-// Algorithmic traffic: 4 B read + 1 B write per voxel (+4 B if out_prob).
-template <int KS>
-__global__ __launch_bounds__(256) void median_harden_c1_kernel(const float *__restrict__ prob, int D,
-                                                               int64_t HW, float thr,
-                                                               uint8_t *__restrict__ out_sem,
-                                                               float *__restrict__ out_prob)
-{
-    constexpr int M = KS / 2;
-    constexpr int PF = 8;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < HW;
-         p += (int64_t)gridDim.x * blockDim.x) {
-        const float *src = prob + p;
-        float win[KS];
-        // slices 0..KS-2 enter the window; the first M of them pass through raw
-#pragma unroll
-        for (int i = 0; i < KS - 1; ++i) win[i] = src[(int64_t)i * HW];
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            out_sem[(int64_t)i * HW + p] = win[i] >= thr ? 1 : 0;
-            if (out_prob) out_prob[(int64_t)i * HW + p] = win[i];
-        }
-        float cur[PF], nxt[PF];
-        const int s_end = D - M;  // filtered slices are [M, s_end)
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            int z = M + u + M;
-            cur[u] = (z < D) ? src[(int64_t)z * HW] : 0.f;
-        }
-        for (int s0 = M; s0 < s_end; s0 += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                int z = s0 + PF + u + M;
-                nxt[u] = (z < D) ? src[(int64_t)z * HW] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                int s = s0 + u;
-                if (s < s_end) {
-                    win[KS - 1] = cur[u];
-                    float med = median_regs<KS>(win);
-                    out_sem[(int64_t)s * HW + p] = med >= thr ? 1 : 0;
-                    if (out_prob) out_prob[(int64_t)s * HW + p] = med;
-                    // slide: the filtered value replaces the raw one (recursive filter)
-                    win[M] = med;
-#pragma unroll
-                    for (int i = 0; i < KS - 1; ++i) win[i] = win[i + 1];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) cur[u] = nxt[u];
-        }
-        // tail: win[M .. KS-2] hold the raw slices D-M .. D-1
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            int s = D - M + i;
-            float v = win[M + i];
-            out_sem[(int64_t)s * HW + p] = v >= thr ? 1 : 0;
-            if (out_prob) out_prob[(int64_t)s * HW + p] = v;
-        }
-    }
-}
-
-// P1+P2, C > 1: same scan, one filter window per channel kept in LDS ([c][k][tid] -> conflict
-// free), argmax over the filtered channels (first maximum wins, like torch.argmax).
-template <int KS>
-__global__ __launch_bounds__(256) void median_harden_mc_kernel(const float *__restrict__ prob, int D,
-                                                               int C, int64_t HW,
-                                                               uint8_t *__restrict__ out_sem,
-                                                               float *__restrict__ out_prob)
-{
-    extern __shared__ float lds[];  // C * KS * blockDim.x
-    constexpr int M = KS / 2;
-    const int tid = threadIdx.x;
-    const int nt = blockDim.x;
-    for (int64_t p0 = (int64_t)blockIdx.x * nt; p0 < HW; p0 += (int64_t)gridDim.x * nt) {
-        int64_t p = p0 + tid;
-        bool live = p < HW;
-        if (live) {
-            for (int c = 0; c < C; ++c)
-                for (int i = 0; i < KS - 1; ++i)
-                    lds[(c * KS + i) * nt + tid] = prob[((int64_t)i * C + c) * HW + p];
-            for (int s = 0; s < D; ++s) {
-                bool filt = (s >= M) && (s < D - M);
-                float best = -INFINITY;
-                int arg = 0;
-                for (int c = 0; c < C; ++c) {
-                    float v;
-                    if (filt) {
-                        float w[KS];
-                        // slot of slice z is z % KS; the incoming slice s+M overwrites s-M-1
-                        lds[(c * KS + (s + M) % KS) * nt + tid] = prob[((int64_t)(s + M) * C + c) * HW + p];
-#pragma unroll
-                        for (int i = 0; i < KS; ++i) w[i] = lds[(c * KS + i) * nt + tid];
-                        v = median_regs<KS>(w);
-                        lds[(c * KS + s % KS) * nt + tid] = v;
-                    } else {
-                        v = (KS == 1) ? prob[((int64_t)s * C + c) * HW + p]
-                                      : lds[(c * KS + s % KS) * nt + tid];
-                    }
-                    if (out_prob) out_prob[((int64_t)s * C + c) * HW + p] = v;
-                    if (v > best) { best = v; arg = c; }
-                }
-                out_sem[(int64_t)s * HW + p] = (uint8_t)arg;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// The same for C <= MC_CMAX channels with the incoming slices PREFETCHED: the loads of the next MC_PF slices (all
-// channels: MC_PF x C dword loads per lane) are in flight while the current slice is filtered -- the form above issues
-// every load right before its use and ran at 0.6 TB/s on C = 5 (one HBM latency per slice and channel, 16 waves per CU).
-// Filtered steps t = 0 .. D - 2M - 1 (slice s = M + t, incoming slice s + M) are unrolled by MC_PF so that the prefetch
-// registers are indexed statically.
+// P1+P2: the recursive median + harden kernels live in emp_median_kernels.inc and are compiled for two slice -> pointer
+// selections (the file undefines the MEDIAN_* macros it was given).  First the whole stack in one tensor, every slice
+// written (emp_median_harden_stack).
 #define MC_PF 4
 #define MC_CMAX 8
-template <int KS>
-__global__ __launch_bounds__(256) void median_harden_mc8_kernel(const float *__restrict__ prob, int D, int C,
-                                                                int64_t HW, uint8_t *__restrict__ out_sem,
-                                                                float *__restrict__ out_prob)
-{
-    extern __shared__ float lds[];  // C * KS * blockDim.x, [c][slot][tid]; a lane only touches its own column
-    constexpr int M = KS / 2;
-    const int tid = threadIdx.x;
-    const int nt = blockDim.x;
-    for (int64_t p = (int64_t)blockIdx.x * nt + tid; p < HW; p += (int64_t)gridDim.x * nt) {
-        const float *src = prob + p;
-        const int64_t cs = HW;                                    // channel stride; slice stride = C * HW
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int i = 0; i < KS - 1; ++i) lds[(c * KS + i) * nt + tid] = src[((int64_t)i * C + c) * cs];
-        float nx[MC_PF][MC_CMAX];
-#pragma unroll
-        for (int j = 0; j < MC_PF; ++j)
-#pragma unroll
-            for (int c = 0; c < MC_CMAX; ++c)
-                nx[j][c] = (c < C && KS - 1 + j < D) ? src[((int64_t)(KS - 1 + j) * C + c) * cs] : 0.f;
-        // the first M slices pass through raw
-        for (int s = 0; s < M; ++s) {
-            float best = -INFINITY;
-            int arg = 0;
-            for (int c = 0; c < C; ++c) {
-                const float v = lds[(c * KS + s) * nt + tid];
-                if (out_prob) out_prob[((int64_t)s * C + c) * cs + p] = v;
-                if (v > best) { best = v; arg = c; }
-            }
-            out_sem[(int64_t)s * HW + p] = (uint8_t)arg;
+#define MEDIAN_KERNEL(form) median_harden_##form##_kernel
+#define MEDIAN_SRC_PARAM const float *__restrict__ prob
+#define MEDIAN_OUT_PROB_PARAM float *__restrict__ out_prob
+#define MEDIAN_LANE(src, p, C) const float *src = prob + p
+#define MEDIAN_LD(src, z, idx) src[idx]
+#define MEDIAN_IF_SEM(s)
+#define MEDIAN_IF_PROB(s) if (out_prob)
+#define MEDIAN_SEM_ROW(s) s
+#define MEDIAN_PROB_ROW(s) s
+#include "emp_median_kernels.inc"
+
+// Then a window of a longer stack (emp_median_harden_window): the kernel walks the virtual stack hist | prob | halo of
+// h + n + l slices (h, l = m or 0), keeps the labels of the n `prob` rows and the filtered values of their last m.
+struct WindowSel {
+    const float *hist, *prob, *halo;  // (h, C, HW) filtered | (n, C, HW) raw | (l, C, HW) raw.  Not __restrict__: the tail
+    int h, n, m;                      // may be written over hist (a lane reads its history before it writes its tail)
+    struct Lane {
+        const float *hist, *prob, *halo;
+        int h, hn;
+        int64_t b1, b2;               // elements of the virtual stack before prob and before halo
+        __device__ __forceinline__ float ld(int z, int64_t idx) const
+        {
+            // the tensor and its offset in the virtual stack are SELECTED (scalar), the load is one: a branch per slice
+            // would end the basic block and, with it, the batch of prefetch loads in flight
+            const float *b = z < h ? hist : (z < hn ? prob : halo);
+            const int64_t at = z < h ? 0 : (z < hn ? b1 : b2);
+            return b[idx - at];
         }
-        const int n_f = D - 2 * M;                                // filtered slices (D >= KS: at least one)
-        int slot_in = (KS - 1) % KS, slot_s = M % KS;             // ring slots of the incoming slice and of slice s
-        for (int t0 = 0; t0 < n_f; t0 += MC_PF) {
-#pragma unroll
-            for (int j = 0; j < MC_PF; ++j) {
-                const int t = t0 + j;
-                if (t < n_f) {                                     // block-uniform
-                    const int s = M + t, zin = s + M;
-                    float best = -INFINITY;
-                    int arg = 0;
-#pragma unroll
-                    for (int c = 0; c < MC_CMAX; ++c) {
-                        if (c < C) {
-                            float w[KS];
-                            lds[(c * KS + slot_in) * nt + tid] = nx[j][c];
-                            nx[j][c] = (zin + MC_PF < D) ? src[((int64_t)(zin + MC_PF) * C + c) * cs] : 0.f;
-#pragma unroll
-                            for (int i = 0; i < KS; ++i) w[i] = lds[(c * KS + i) * nt + tid];
-                            const float v = median_regs<KS>(w);
-                            lds[(c * KS + slot_s) * nt + tid] = v;        // recursive: later windows see the filtered value
-                            if (out_prob) out_prob[((int64_t)s * C + c) * cs + p] = v;
-                            if (v > best) { best = v; arg = c; }
-                        }
-                    }
-                    out_sem[(int64_t)s * HW + p] = (uint8_t)arg;
-                    slot_in = slot_in + 1 == KS ? 0 : slot_in + 1;
-                    slot_s = slot_s + 1 == KS ? 0 : slot_s + 1;
-                }
-            }
-        }
-        // the last M slices pass through raw
-        for (int s = D - M; s < D; ++s) {
-            float best = -INFINITY;
-            int arg = 0;
-            for (int c = 0; c < C; ++c) {
-                const float v = lds[(c * KS + s % KS) * nt + tid];
-                if (out_prob) out_prob[((int64_t)s * C + c) * cs + p] = v;
-                if (v > best) { best = v; arg = c; }
-            }
-            out_sem[(int64_t)s * HW + p] = (uint8_t)arg;
-        }
+    };
+    __device__ __forceinline__ Lane lane(int64_t p, int64_t slice) const
+    {
+        return Lane{hist + p, prob + p, halo + p, h, h + n, h * slice, (h + n) * slice};
     }
-}
+    __device__ __forceinline__ bool keeps_sem(int s) const { return s >= h && s < h + n; }
+    __device__ __forceinline__ bool keeps_prob(int s) const { return s >= h + n - m && s < h + n; }
+    __device__ __forceinline__ int sem_row(int s) const { return s - h; }
+    __device__ __forceinline__ int prob_row(int s) const { return s - (h + n - m); }
+};
+#define MEDIAN_KERNEL(form) median_window_##form##_kernel
+#define MEDIAN_SRC_PARAM const WindowSel sel
+#define MEDIAN_OUT_PROB_PARAM float *out_prob
+#define MEDIAN_LANE(src, p, C) const WindowSel::Lane src = sel.lane(p, (int64_t)(C) * HW)
+#define MEDIAN_LD(src, z, idx) src.ld(z, idx)
+#define MEDIAN_IF_SEM(s) if (sel.keeps_sem(s))
+#define MEDIAN_IF_PROB(s) if (out_prob && sel.keeps_prob(s))
+#define MEDIAN_SEM_ROW(s) sel.sem_row(s)
+#define MEDIAN_PROB_ROW(s) sel.prob_row(s)
+#include "emp_median_kernels.inc"
 
 template <int KS>
 static int launch_median(const float *prob, int D, int C, int64_t HW, float thr, uint8_t *out_sem,
@@ -286,6 +145,69 @@ extern "C" int emp_harden(const float *prob, int D, int C, int64_t HW, float thr
                           void *stream)
 {
     return emp_median_harden_stack(prob, D, C, HW, 1, thr, out_sem, nullptr, stream);
+}
+
+// the window form: same grid, same LDS, same choice of kernel as launch_median; Dv = slices of hist | prob | halo
+template <int KS>
+static int launch_median_window(const WindowSel &sel, int Dv, int C, int64_t HW, float thr, uint8_t *out_sem,
+                                float *out_tail, hipStream_t st)
+{
+    const int block = 256;
+    int grid = emp_grid(HW, block, 8192);
+    if (C == 1) {
+        hipLaunchKernelGGL(median_window_c1_kernel<KS>, dim3(grid), dim3(block), 0, st, sel, Dv, HW, thr, out_sem,
+                           out_tail);
+    } else {
+        size_t lds = (size_t)C * KS * block * sizeof(float);
+        if (C <= MC_CMAX) {
+            if (lds > 64 * 1024)
+                hipFuncSetAttribute((const void *)median_window_mc8_kernel<KS>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(median_window_mc8_kernel<KS>, dim3(grid), dim3(block), lds, st, sel, Dv, C, HW,
+                               out_sem, out_tail);
+        } else {
+            if (lds > 64 * 1024)
+                hipFuncSetAttribute((const void *)median_window_mc_kernel<KS>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(median_window_mc_kernel<KS>, dim3(grid), dim3(block), lds, st, sel, Dv, C, HW,
+                               out_sem, out_tail);
+        }
+    }
+    EMP_CHECK_LAUNCH("emp_median_harden_window");
+    return EMP_OK;
+}
+
+extern "C" int emp_median_harden_window(const float *hist, const float *prob, const float *halo, int D, int C,
+                                        int64_t HW, int ks, float thr, uint8_t *out_sem, float *out_tail,
+                                        void *stream)
+{
+    EMP_REQUIRE(prob && out_sem, "median window: null pointer");
+    EMP_REQUIRE(ks >= 1 && ks <= EMP_MAX_KS && (ks & 1), "median window: ks=%d must be odd in 1..%d", ks, EMP_MAX_KS);
+    EMP_REQUIRE(C >= 1 && C <= EMP_MAX_CLASSES, "median window: C=%d out of range", C);
+    EMP_REQUIRE(HW >= 0, "median window: negative size");
+    const int m = ks / 2;
+    EMP_REQUIRE(D >= (m > 1 ? m : 1), "median window: D=%d slices, at least max(ks/2, 1)=%d needed (ks=%d)", D,
+                m > 1 ? m : 1, ks);
+    if (ks == 1) {
+        EMP_REQUIRE(!hist && !halo && !out_tail, "median window: ks=1 hardens only: hist, halo and out_tail must be NULL");
+        return emp_median_harden_stack(prob, D, C, HW, 1, thr, out_sem, nullptr, stream);
+    }
+    const int h = hist ? m : 0, l = halo ? m : 0;
+    EMP_REQUIRE(h + D + l >= ks, "median window: hist | prob | halo is %d + %d + %d slices, shorter than ks=%d", h, D, l,
+                ks);
+    if (C > 1 && (size_t)C * ks * 256 * sizeof(float) > 160 * 1024)
+        EMP_FAIL(EMP_EINVAL, "median window: C*ks too large for LDS (%d x %d)", C, ks);
+    if (HW == 0) return EMP_OK;
+    hipStream_t st = emp_stream(stream);
+    const WindowSel sel{hist, prob, halo, h, D, m};
+    const int Dv = h + D + l;
+    switch (ks) {
+        case 3: return launch_median_window<3>(sel, Dv, C, HW, thr, out_sem, out_tail, st);
+        case 5: return launch_median_window<5>(sel, Dv, C, HW, thr, out_sem, out_tail, st);
+        case 7: return launch_median_window<7>(sel, Dv, C, HW, thr, out_sem, out_tail, st);
+        case 9: return launch_median_window<9>(sel, Dv, C, HW, thr, out_sem, out_tail, st);
+        default: return launch_median_window<11>(sel, Dv, C, HW, thr, out_sem, out_tail, st);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

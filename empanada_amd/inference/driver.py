@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..data import DeviceVolume
-from . import sharded
+from . import sharded, windowed
 from .engines import logits_to_prob
 
 __all__ = ['infer_volume']
@@ -49,9 +49,70 @@ def _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps):
     return {k: torch.cat(v, dim=0).contiguous() for k, v in outs.items()}
 
 
+def _check_windows(window_slices, mem_budget, pipeline, world):
+    """argument errors of the window switch, before any GPU work"""
+    w = window_slices
+    if w is not None and w != 'auto' and (isinstance(w, bool) or not isinstance(w, (int, np.integer)) or w < 1):
+        raise ValueError(f"window_slices must be None, a positive number of slices or 'auto', got {w!r}")
+    if mem_budget is not None:
+        if isinstance(mem_budget, bool) or not isinstance(mem_budget, (int, np.integer)) or mem_budget < 1:
+            raise ValueError(f"mem_budget must be a positive number of bytes, got {mem_budget!r}")
+        if pipeline is not None:
+            raise ValueError(f"mem_budget={mem_budget} given together with a pipeline: with pipeline= the pipeline's own "
+                             "mem_budget serves window_slices='auto'")
+    if w is not None and world > 1:
+        raise ValueError(f"window_slices={w!r} with {world} ranks: windows within a rank's block are not built yet "
+                         "(the hand-over across ranks stays as it is); leave window_slices=None")
+    return w if w is None or w == 'auto' else int(w)
+
+
+def _model_classes(engine, dv, axis, margs):
+    """channels of the semantic head: what the model says, or what it returns for one slice"""
+    c = int(getattr(engine.model, 'num_classes', 0))
+    if not c:
+        with torch.no_grad():
+            c = int(engine.model(dv.batch(axis, 0, 1), *margs)['sem_logits'].shape[1])
+    return c
+
+
+@torch.no_grad()
+def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
+    """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`, every batch
+    written once into the window's head buffers instead of collected and concatenated"""
+    hp, wp = dv.padded_shape(axis)
+    per = max(1, batch_pixels // (hp * wp * dv.scale ** 2))
+    render = hasattr(engine, 'coarse_boundaries')
+    margs = (render_steps, not engine.coarse_boundaries) if render else ()
+    shapes = windowed.head_shapes(hp, wp, _model_classes(engine, dv, axis, margs), dv.scale if render else 1,
+                                  render and bool(engine.coarse_boundaries))
+    m = int(params['median_kernel_size']) // 2
+    budget = mem_budget
+    if window_slices == 'auto' and budget is None:
+        budget = torch.cuda.mem_get_info(dv.vol.device)[0] - 4 * n * shapes['sem'][1] * shapes['sem'][2]   # less `pan`
+    sem_bytes = 4 * int(np.prod(shapes['sem']))
+    plan = windowed.plan_windows(n, per, m, window_slices, windowed.bytes_per_slice(shapes), budget, sem_bytes)
+
+    def fill(lo, hi, bufs, at):
+        for s in range(lo, hi, per):
+            e = min(hi, s + per)
+            x = dv.batch(axis, s, e).contiguous(memory_format=torch.channels_last)
+            o = engine.model(x, *margs)
+            j = at + s - lo
+            bufs['sem'][j:j + e - s].copy_(logits_to_prob(o['sem_logits']))
+            bufs['ctr_hmp'][j:j + e - s].copy_(o['ctr_hmp'])
+            bufs['offsets'][j:j + e - s].copy_(o['offsets'])
+
+    step = {}
+    pan = windowed.windowed_panoptic_stack(fill, plan, shapes, device=dv.vol.device, info=step, **params)
+    info['windows'][axis] = step['windows']
+    info['head_bytes'] = max(info['head_bytes'], step['head_bytes'])
+    return pan
+
+
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
-                 out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None):
+                 out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
+                 window_slices=None, mem_budget=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -66,9 +127,16 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     graph replay, heads written in place and two streams; its own batch_pixels sizes the model calls (passing another
     value here as well is an error).  The result gains 'pipeline': what ran.
     batch_pixels: output pixels per model call; None = 32 Mi pixels, or the pipeline's value with pipeline=.
+    window_slices: None = the heads of a whole plane are resident before its post-processing starts (4 (C + 3) bytes per
+    voxel of the plane); an integer W or 'auto' = the plane streams through windows of W slices
+    (inference/windowed.py): W + m slices of heads (m = ks // 2) and the plane's uint32 labels are all that is resident,
+    the volumes are the same.  W is rounded down to a multiple of the slices per model call; 'auto' takes the whole
+    plane when it fits into mem_budget bytes (None: the free device memory) and the largest window that does otherwise.
+    The result gains 'windows': {axis: steps} and 'head_bytes': bytes of head buffers held.  Not with several ranks.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
+    window_slices = _check_windows(window_slices, mem_budget, pipeline, world)
     labels = list(labels)
     thing_list = list(engine.thing_list)
     div = engine.label_divisor
@@ -116,15 +184,19 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
 
     if pipeline is not None:
         return pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
-                            track=track, finish=finish, class_names=class_names, out=out)
+                            track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices)
     planes, base = {}, 0
+    windows = {'windows': {}, 'head_bytes': 0}
     for axis in axes:
         n = dv.n_slices(axis)
-        b = sharded.shard_bounds(n, world)
-        lo, hi = int(b[rank]), int(b[rank + 1])
-        heads = _plane_heads(engine, dv, axis, lo, hi, batch_pixels, steps)
-        pan = sharded.sharded_panoptic_stack(heads['sem'], heads['ctr_hmp'], heads['offsets'], group=group, **params)
-        del heads
+        if window_slices is not None:
+            pan = _plane_windowed(engine, dv, axis, n, batch_pixels, steps, params, window_slices, mem_budget, windows)
+        else:
+            b = sharded.shard_bounds(n, world)
+            lo, hi = int(b[rank]), int(b[rank + 1])
+            heads = _plane_heads(engine, dv, axis, lo, hi, batch_pixels, steps)
+            pan = sharded.sharded_panoptic_stack(heads['sem'], heads['ctr_hmp'], heads['offsets'], group=group, **params)
+            del heads
         planes[axis] = track(pan, axis, base)
         base += planes[axis].n_inst
         del pan
@@ -142,4 +214,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
             datasets[c] = out[names[c]]
             host = vols[c].view(torch.int32).cpu().numpy().view(np.uint32) if c in thing_list else vols[c].cpu().numpy()
             datasets[c].write_slab(z0, host)
-    return {'volumes': vols, 'z_range': (z0, z1), 'instances': counts, 'datasets': datasets}
+    res = {'volumes': vols, 'z_range': (z0, z1), 'instances': counts, 'datasets': datasets}
+    if window_slices is not None:
+        res.update(windows)
+    return res

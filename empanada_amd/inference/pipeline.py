@@ -16,6 +16,8 @@ What it changes against the plain call (driver._plane_heads + the serial plane l
     'auto' falls back to one set and serial planes when two planes' heads do not fit;
   * writing: the labelled slab goes to the zarr array through SlabWriter (pinned buffer, asynchronous copy, chunk files
     written by a pool while the next class is copied).
+With infer_volume(..., window_slices=) the planes stream through windows of slices (inference/windowed.py) and the two
+sets of buffers alternate per step of a plane instead of per plane (_run_windowed).
 """
 import json
 import os
@@ -25,7 +27,7 @@ import torch
 
 from .. import _hip
 from ..zarr_utils import SlabWriter, ZarrV2Array
-from . import sharded
+from . import sharded, windowed
 from .engines import logits_to_prob
 
 __all__ = ['VolumePipeline']
@@ -256,9 +258,14 @@ class VolumePipeline:
         torch.cuda.synchronize(dv.vol.device)
 
     # ------------------------------------------------------------------------------------------ the volume
-    def run(self, dv, *, axes, labels, thing_list, params, steps, group, track, finish, class_names, out):
+    def run(self, dv, *, axes, labels, thing_list, params, steps, group, track, finish, class_names, out,
+            window_slices=None):
         """Called by infer_volume after its own argument checks.  track(pan, axis, base) and finish(planes) are the
-        driver's own plane and volume steps, so both paths share them."""
+        driver's own plane and volume steps, so both paths share them.  window_slices: see _run_windowed."""
+        if window_slices is not None:
+            return self._run_windowed(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps,
+                                      track=track, finish=finish, class_names=class_names, out=out,
+                                      window_slices=window_slices)
         engine = self.engine
         dev = dv.vol.device
         rank, world = sharded._world(group)
@@ -351,6 +358,120 @@ class VolumePipeline:
         return {'volumes': vols, 'z_range': (z0, z1), 'instances': counts, 'datasets': datasets,
                 'pipeline': {'tuned': self.tuned_counts(), 'graph': bool(graph), 'overlap': bool(overlap),
                              'head_bytes': int(head_bytes),
+                             'captures': (self._graphed.captures - captured) if graph else 0}}
+
+    # ------------------------------------------------------------------------------------------ the volume, in windows
+    def _run_windowed(self, dv, *, axes, labels, thing_list, params, steps, track, finish, class_names, out,
+                      window_slices):
+        """run() with every plane streamed through windows of slices (inference/windowed.py; one rank).  The two sets of
+        head buffers alternate per STEP instead of per plane: the forward of step k + 1 runs on the forward stream
+        while the post stream labels step k; with overlap off, one set and strict alternation.  The carry copy and the
+        median are ordinary launches on the two streams, outside the captured forward, under the same events that
+        order the sets.  'auto' plans with the pipeline's mem_budget (None: the free device memory), halved when two
+        sets are held."""
+        engine, dev = self.engine, dv.vol.device
+        render = hasattr(engine, 'coarse_boundaries')
+        coarse = bool(getattr(engine, 'coarse_boundaries', False))
+        margs = self._margs(steps)
+        fp32 = self._param().dtype == torch.float32
+        ks = int(params['median_kernel_size'])
+        m = ks // 2
+        geo = [(axis, dv.n_slices(axis), self._per(dv, axis)) + tuple(dv.padded_shape(axis)) for axis in axes]
+        self._tune_once((geo[0][2], geo[0][3], geo[0][4]), margs, None)
+        classes = int(getattr(self.model, 'num_classes', 0))
+        if not classes:                                   # a model that does not say: ask it on one slice
+            with torch.no_grad():
+                classes = int(self.model(dv.batch(geo[0][0], 0, 1).to(self._param().dtype), *margs)['sem_logits'].shape[1])
+        shapes = [windowed.head_shapes(hp, wp, classes, dv.scale if render else 1, render and coarse)
+                  for _, _, _, hp, wp in geo]
+        budget = self.mem_budget
+        if budget is None:
+            free, _ = torch.cuda.mem_get_info(dev)
+            cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+            held = 4 * sum(s.numel() for s in self._store if s is not None)
+            budget = max(0, free + cached + held - 4 * max(n * sh['sem'][1] * sh['sem'][2]
+                                                           for (_, n, _, _, _), sh in zip(geo, shapes)))
+        nsets = 1 if self.overlap is False else 2
+        while True:
+            plans = [windowed.plan_windows(n, per, m, window_slices, windowed.bytes_per_slice(sh), budget // nsets,
+                                           4 * int(np.prod(sh['sem']))) for (_, n, per, _, _), sh in zip(geo, shapes)]
+            lay = [windowed.plane_layout(p, ks) for p in plans]
+            elems = [self._elems({k: (cap,) + tuple(v) for k, v in sh.items()}) for (_, _, cap), sh in zip(lay, shapes)]
+            if nsets == 1 or self.overlap is True or window_slices == 'auto' or 8 * max(elems) <= budget:
+                break
+            nsets = 1                                     # overlap='auto' and two sets of these windows do not fit
+        overlap = nsets == 2
+        if any(borrow for _, borrow, _ in lay):
+            nsets = 2                                     # windows shorter than the filter borrow their halo from a second set
+        if nsets == 1:
+            self._store[1] = None
+        for k in range(nsets):
+            self._reserve(k, max(elems), dev)
+        if self._streams is None or self._streams[0].device != dev:
+            self._streams = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
+        fwd, post = self._streams
+        graph = self.graph and fp32
+        if graph and self._graphed is None:
+            from ..models.graphed import GraphedForward
+            self._graphed = GraphedForward(self.model, warmup=1, max_graphs=24, clone_outputs=False)
+        model = self._graphed if graph else self.model
+        defer = self._defers()
+        captured = self._graphed.captures if graph else 0
+
+        cur = torch.cuda.current_stream(dev)
+        fwd.wait_stream(cur)
+        post.wait_stream(cur)
+        last_read = {}                                    # set -> event: the last post-processing that read it
+        planes, base, counts_w, hist_bytes = {}, 0, {}, 0
+        try:
+            if defer:
+                self.model.defer_up4 = True
+            with torch.cuda.stream(post):
+                for (axis, n, per, hp, wp), sh, plan in zip(geo, shapes, plans):
+                    def fill(lo, hi, bufs, at, axis=axis, per=per):
+                        self._forward(model, dv, axis, lo, hi, per, margs,
+                                      {k: v[at:at + hi - lo] for k, v in bufs.items()})
+
+                    P = windowed.WindowedPlane(fill, plan, sh, device=dev, sets=nsets,
+                                               alloc=lambda i, shp: self._views(i, shp), **params)
+                    K = len(P.steps)
+                    done = [torch.cuda.Event() for _ in range(K)]
+                    ahead = 1 if (overlap and not P.borrow) else 0
+                    f = 0
+                    for k in range(K):
+                        while f <= min(K - 1, P.needs(k) + ahead):
+                            with torch.cuda.stream(fwd):
+                                if f % len(P.sets) in last_read:
+                                    fwd.wait_event(last_read[f % len(P.sets)])
+                                P.forward(f)
+                                done[f].record(fwd)
+                            f += 1
+                        post.wait_event(done[P.needs(k)])
+                        P.post(k)
+                        ev = torch.cuda.Event()
+                        ev.record(post)
+                        last_read[k % len(P.sets)] = ev
+                        if P.borrow:
+                            last_read[(k + 1) % len(P.sets)] = ev
+                    counts_w[axis] = K
+                    hist_bytes = max(hist_bytes, 0 if P.hist is None else P.hist.numel() * 4)
+                    planes[axis] = track(P.pan, axis, base)
+                    base += planes[axis].n_inst
+                    del P
+                vols, (z0, z1), counts = finish(planes)
+                datasets = self._write(out, vols, z0, labels, thing_list, class_names, dv.shape, 0, 1, None, post)
+        finally:
+            if defer:
+                self.model.defer_up4 = False
+        cur.wait_stream(post)
+        cur.wait_stream(fwd)
+        for v in vols.values():
+            v.record_stream(cur)
+        head_bytes = 4 * sum(s.numel() for s in self._store if s is not None) + hist_bytes
+        return {'volumes': vols, 'z_range': (z0, z1), 'instances': counts, 'datasets': datasets,
+                'windows': counts_w, 'head_bytes': int(head_bytes),
+                'pipeline': {'tuned': self.tuned_counts(), 'graph': bool(graph), 'overlap': bool(overlap),
+                             'head_bytes': int(head_bytes), 'windows': counts_w,
                              'captures': (self._graphed.captures - captured) if graph else 0}}
 
     # ------------------------------------------------------------------------------------------ writing

@@ -346,6 +346,24 @@ int emp_upsample_bilinear_prob(const float *x, int N, int C, int h, int w, const
 int emp_median_harden_stack(const float *prob, int D, int C, int64_t HW, int ks, float thr,
                             uint8_t *out_sem, float *out_prob, void *stream);
 
+/* The same filter on a WINDOW of a longer stack, so that the stack never has to be resident at once.
+ * prob  (D, C, HW): the window's raw probabilities.
+ * hist  (m, C, HW) or NULL: the FILTERED probabilities of the m = ks/2 slices before the window; NULL = the window
+ *       starts the axis (its first m slices pass through raw and serve as history, as in emp_median_harden_stack).
+ * halo  (m, C, HW) or NULL: the RAW probabilities of the m slices after the window; NULL = the window ends the axis
+ *       (its last m slices pass through raw).
+ * out_sem  (D, HW) u8, hardened as emp_median_harden_stack does.
+ * out_tail (m, C, HW) or NULL: what the filter left for the window's last m slices = the next window's hist.  It may
+ *       be the same buffer as hist: a lane reads its history before it writes its tail.
+ * With S = hist | prob | halo (absent parts left out), out_sem equals rows [len(hist), len(hist) + D) of the out_sem
+ * emp_median_harden_stack(S) writes and out_tail the rows [len(hist) + D - m, len(hist) + D) of its out_prob, bit for
+ * bit: cutting a stack into windows and carrying the tail reproduces the whole-stack result.  Nothing is concatenated
+ * and no full-size out_prob exists: 4 B read + 1 B written per voxel and channel, plus the m-slice ends.
+ * Requires D >= max(m, 1) and, for ks > 1, len(hist) + D + len(halo) >= ks.  ks == 1 hardens only: hist, halo and
+ * out_tail must be NULL.  The LDS ceiling of emp_median_harden_stack applies (C > 1: C * ks <= 160).              */
+int emp_median_harden_window(const float *hist, const float *prob, const float *halo, int D, int C, int64_t HW,
+                             int ks, float thr, uint8_t *out_sem, float *out_tail, void *stream);
+
 /* One streaming step of the same filter: median over ks slices of n floats each.
  * slices_host: host array of ks device pointers; out may alias any of them.
  * replaces _MedianQueue.get_median                 engines.py:59-66                             */

@@ -9,6 +9,10 @@ two device synchronisations.  One JSON line.
 
     python tools/bench_infer_volume.py --size 512 [--model pdl_r50|mitonet_pr] [--axes xy,xz,yz] [--paths plain,pipeline]
                                        [--repeats 3] [--warmup 1] [--no-tune] [--no-graph] [--overlap auto|on|off]
+                                       [--window-slices W|auto]
+
+--window-slices streams every plane through windows of W slices (inference/windowed.py) on the paths named; the row then
+holds the steps per plane and the bytes of head buffers held (profiles/windowed_planes.md).
 
 --split also times the forwards of the three planes alone (heads written in place, no post-processing) on the pipeline's
 own code, so that a volume whose random heads make the post-processing dominate can be read.
@@ -85,6 +89,7 @@ def main():
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--overlap', default='auto', choices=['auto', 'on', 'off'])
     ap.add_argument('--split', action='store_true', help='also time the forwards alone')
+    ap.add_argument('--window-slices', default=None, help="slices per window, or 'auto'; default: whole planes")
     ap.add_argument('--out', default=None, help='write the JSON line to this file as well')
     args = ap.parse_args()
     _hip.require_gpu()
@@ -100,7 +105,10 @@ def main():
     base = '/dev/shm' if os.path.isdir('/dev/shm') else tempfile.gettempdir()
     store = tempfile.mkdtemp(prefix='emp_infer_volume_', dir=base)
     kw = dict(norms=NORMS, labels=[1], axes=axes, class_names={1: 'mito'}, out=ZarrV2Group(store))
+    if args.window_slices is not None:
+        kw['window_slices'] = 'auto' if args.window_slices == 'auto' else int(args.window_slices)
     row = {'size': args.size, 'model': args.model, 'axes': list(axes), 'batch_pixels': args.batch_pixels,
+           'window_slices': kw.get('window_slices'),
            'device': torch.cuda.get_device_name(0), 'repeats': args.repeats, 'warmup': args.warmup}
     fns, pipe, last = {}, None, {}
     try:
@@ -135,6 +143,7 @@ def main():
                               'spread_s': round(max(times) - min(times), 4),
                               'Mvox_per_s': round(args.size ** 3 / sorted(times)[len(times) // 2] / 1e6, 2),
                               'instances': int(res['instances'][1]),
+                              'windows': res.get('windows'), 'head_bytes': res.get('head_bytes'),
                               'labelled_share': round(float((res['volumes'][1].view(torch.int32) != 0).float().mean()), 5)})
         if pipe is not None:
             row['pipeline']['pipeline'] = last['pipeline']['pipeline']
