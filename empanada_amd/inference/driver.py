@@ -18,6 +18,7 @@ tools/bench_infer_volume.py.
 import numpy as np
 import torch
 
+from .. import _hip
 from ..data import DeviceVolume
 from . import sharded, windowed
 from .engines import logits_to_prob
@@ -25,28 +26,118 @@ from .engines import logits_to_prob
 __all__ = ['infer_volume']
 
 _AXES = {'xy': 0, 'xz': 1, 'yz': 2}
+_HEADS = (('sem', 'sem_logits'), ('ctr_hmp', 'ctr_hmp'), ('offsets', 'offsets'))
+
+
+# ---------------------------------------------------------------- the facts of a plane, shared with inference/pipeline.py
+def slices_per_call(dv, axis, batch_pixels):
+    """batch_pixels counts OUTPUT pixels: with a down-sampling volume (dv.scale = f > 1) the semantic head comes out at
+    f x the padded input, so batch_pixels keeps bounding the memory"""
+    hp, wp = dv.padded_shape(axis)
+    return max(1, batch_pixels // (hp * wp * dv.scale ** 2))
+
+
+def model_args(engine, steps):
+    """extra positional arguments of the model's forward: (render_steps, interpolate_ins) for the PointRend ("render")
+    engines, none for the plain ones"""
+    return (steps, not engine.coarse_boundaries) if hasattr(engine, 'coarse_boundaries') else ()
+
+
+def model_classes(model, dv, axis, margs):
+    """channels of the semantic head: what the model says, or what it returns for one slice"""
+    c = int(getattr(model, 'num_classes', 0))
+    if not c:
+        with torch.no_grad():
+            x = dv.batch(axis, 0, 1).to(next(model.parameters()).dtype)
+            c = int(model(x, *margs)['sem_logits'].shape[1])
+    return c
+
+
+def plane_head_shapes(engine, dv, axis, classes):
+    """per-slice shapes of the plane's heads at the padded size (the reference pads every slice to a multiple of
+    padding_factor and crops the labels, engines.py:351-394); n slices of them are (n,) + shape"""
+    render = hasattr(engine, 'coarse_boundaries')
+    return windowed.head_shapes(*dv.padded_shape(axis), classes, dv.scale if render else 1,
+                                render and bool(engine.coarse_boundaries))
+
+
+def write_heads(o, views):
+    """the three heads of one model call, each written once into its (slices,) + shape fp32 view: a head the model left at
+    quarter resolution (`deferred_up4`) is up-sampled into it, the semantic logits become probabilities on the way"""
+    deferred = o.get('deferred_up4', ())
+    for name, key in _HEADS:
+        t, view = o[key], views[name]
+        up = key in deferred
+        if tuple(view.shape[:2] if up else view.shape) != tuple(t.shape[:2] if up else t.shape):
+            raise RuntimeError(f"head {key}: the model returned {tuple(t.shape)}, the plane buffer holds "
+                               f"{tuple(view.shape)}")
+        if up:
+            _hip.upsample_bilinear_prob(t, view.shape[2:], out=view, prob=name == 'sem')
+        elif name != 'sem':
+            view.copy_(t)
+        elif t.dtype == torch.float32:
+            _hip.logits_to_prob(t, out=view)
+        else:
+            view.copy_(logits_to_prob(t))
 
 
 @torch.no_grad()
+def forward_heads(model, margs, dv, axis, lo, hi, per, bufs, at=0):
+    """slices [lo, hi) of the plane through the model in calls of `per`, on the current stream; the heads of slice s go to
+    bufs[name][at + s - lo].  A GraphedForward's static input, once captured, is filled by the slice feeder itself"""
+    hp, wp = dv.padded_shape(axis)
+    dtype = next(model.parameters()).dtype
+    static = getattr(model, 'input_buffer', None)
+    for s in range(lo, hi, per):
+        e = min(hi, s + per)
+        x = dv.batch(axis, s, e, out=static((e - s, 1, hp, wp), args=margs) if static else None)
+        if x.dtype != dtype:
+            x = x.to(dtype)
+        # the model's own outputs are not kept past this line: the next call's activations find that memory free
+        write_heads(model(x.contiguous(memory_format=torch.channels_last), *margs),
+                    {k: v[at + s - lo:at + e - lo] for k, v in bufs.items()})
+
+
+def open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group):
+    """{class: the '<class name>_pred' array of `out`, or None without one}: uint32 for thing classes, uint8 for stuff,
+    chunks (1, Y, X) (pdl_inference3d.py:225-233); rank 0 creates them before any rank opens one"""
+    if out is None:
+        return {c: None for c in labels}
+    names = {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}
+    if rank == 0:
+        for c in labels:
+            out.create_dataset(names[c], shape=shape3d, dtype=np.uint32 if c in thing_list else np.uint8,
+                               overwrite=True, chunks=(1, None, None))
+    if world > 1:
+        torch.distributed.barrier(group=group)
+    return {c: out[names[c]] for c in labels}
+
+
+def host_slab(vol, thing):
+    """a labelled device slab as the numpy array write_slab takes"""
+    return vol.view(torch.int32).cpu().numpy().view(np.uint32) if thing else vol.cpu().numpy()
+
+
+def result(vols, z_range, counts, datasets, windows=None, head_bytes=0, pipeline=None):
+    """infer_volume's result; windows ({axis: steps}): a windowed call, which also reports the head buffers it held"""
+    res = {'volumes': vols, 'z_range': z_range, 'instances': counts, 'datasets': datasets}
+    if windows is not None:
+        res.update(windows=windows, head_bytes=int(head_bytes))
+    if pipeline is not None:
+        res['pipeline'] = pipeline
+    return res
+
+
+# ---------------------------------------------------------------------------------------------- the plain call's planes
+@torch.no_grad()
 def _plane_heads(engine, dv, axis, lo, hi, batch_pixels, render_steps):
     """model forward over slices [lo, hi) of one plane -> resident {'sem' probabilities, 'ctr_hmp', 'offsets'} at the
-    padded size (the reference pads every slice to a multiple of padding_factor and crops the labels, engines.py:351-394).
-    With a down-sampling volume (dv.scale = f > 1, render_steps = 2 + log2 f) the semantic head comes out at f x the
-    padded input, so the slices per call are sized by the output pixels: batch_pixels keeps bounding the memory"""
-    hp, wp = dv.padded_shape(axis)
-    per = max(1, batch_pixels // (hp * wp * dv.scale ** 2))
-    render = hasattr(engine, 'coarse_boundaries')                      # the PointRend ("render") engines
-    outs = {'sem': [], 'ctr_hmp': [], 'offsets': []}
-    for s in range(lo, hi, per):
-        x = dv.batch(axis, s, min(hi, s + per)).contiguous(memory_format=torch.channels_last)
-        if render:
-            o = engine.model(x, render_steps, interpolate_ins=not engine.coarse_boundaries)
-        else:
-            o = engine.model(x)
-        outs['sem'].append(logits_to_prob(o['sem_logits']).float())
-        outs['ctr_hmp'].append(o['ctr_hmp'].float())
-        outs['offsets'].append(o['offsets'].float())
-    return {k: torch.cat(v, dim=0).contiguous() for k, v in outs.items()}
+    padded size, every model call writing its slices of the three buffers"""
+    margs = model_args(engine, render_steps)
+    shapes = plane_head_shapes(engine, dv, axis, model_classes(engine.model, dv, axis, margs))
+    heads = {k: torch.empty((hi - lo,) + s, dtype=torch.float32, device=dv.vol.device) for k, s in shapes.items()}
+    forward_heads(engine.model, margs, dv, axis, lo, hi, slices_per_call(dv, axis, batch_pixels), heads)
+    return heads
 
 
 def _check_windows(window_slices, mem_budget, pipeline, world):
@@ -66,25 +157,12 @@ def _check_windows(window_slices, mem_budget, pipeline, world):
     return w if w is None or w == 'auto' else int(w)
 
 
-def _model_classes(engine, dv, axis, margs):
-    """channels of the semantic head: what the model says, or what it returns for one slice"""
-    c = int(getattr(engine.model, 'num_classes', 0))
-    if not c:
-        with torch.no_grad():
-            c = int(engine.model(dv.batch(axis, 0, 1), *margs)['sem_logits'].shape[1])
-    return c
-
-
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
-    """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`, every batch
-    written once into the window's head buffers instead of collected and concatenated"""
-    hp, wp = dv.padded_shape(axis)
-    per = max(1, batch_pixels // (hp * wp * dv.scale ** 2))
-    render = hasattr(engine, 'coarse_boundaries')
-    margs = (render_steps, not engine.coarse_boundaries) if render else ()
-    shapes = windowed.head_shapes(hp, wp, _model_classes(engine, dv, axis, margs), dv.scale if render else 1,
-                                  render and bool(engine.coarse_boundaries))
+    """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
+    per = slices_per_call(dv, axis, batch_pixels)
+    margs = model_args(engine, render_steps)
+    shapes = plane_head_shapes(engine, dv, axis, model_classes(engine.model, dv, axis, margs))
     m = int(params['median_kernel_size']) // 2
     budget = mem_budget
     if window_slices == 'auto' and budget is None:
@@ -93,14 +171,7 @@ def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, win
     plan = windowed.plan_windows(n, per, m, window_slices, windowed.bytes_per_slice(shapes), budget, sem_bytes)
 
     def fill(lo, hi, bufs, at):
-        for s in range(lo, hi, per):
-            e = min(hi, s + per)
-            x = dv.batch(axis, s, e).contiguous(memory_format=torch.channels_last)
-            o = engine.model(x, *margs)
-            j = at + s - lo
-            bufs['sem'][j:j + e - s].copy_(logits_to_prob(o['sem_logits']))
-            bufs['ctr_hmp'][j:j + e - s].copy_(o['ctr_hmp'])
-            bufs['offsets'][j:j + e - s].copy_(o['offsets'])
+        forward_heads(engine.model, margs, dv, axis, lo, hi, per, bufs, at)
 
     step = {}
     pan = windowed.windowed_panoptic_stack(fill, plan, shapes, device=dv.vol.device, info=step, **params)
@@ -201,20 +272,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         base += planes[axis].n_inst
         del pan
     vols, (z0, z1), counts = finish(planes)
-    datasets = {c: None for c in labels}
+    datasets = open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group)
     if out is not None:
-        names = {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}
-        if rank == 0:
-            for c in labels:
-                out.create_dataset(names[c], shape=shape3d, dtype=np.uint32 if c in thing_list else np.uint8,
-                                   overwrite=True, chunks=(1, None, None))
-        if world > 1:
-            torch.distributed.barrier(group=group)
         for c in labels:
-            datasets[c] = out[names[c]]
-            host = vols[c].view(torch.int32).cpu().numpy().view(np.uint32) if c in thing_list else vols[c].cpu().numpy()
-            datasets[c].write_slab(z0, host)
-    res = {'volumes': vols, 'z_range': (z0, z1), 'instances': counts, 'datasets': datasets}
-    if window_slices is not None:
-        res.update(windows)
-    return res
+            datasets[c].write_slab(z0, host_slab(vols[c], c in thing_list))
+    return result(vols, (z0, z1), counts, datasets, **(windows if window_slices is not None else {}))

@@ -92,3 +92,27 @@ def test_infer_volume_equals_manual_composition(tmp_path, axes, render):
         np.testing.assert_array_equal(arr[...], exp[c])
     assert res['instances'][1] == len(np.unique(exp[1])) - 1
     assert exp[1].max() > 0 or exp[2].max() > 0, "the random model should segment something"
+
+
+@pytest.mark.parametrize('render', [False, True])
+def test_small_batches_fill_the_plane_buffers_like_one_call(render):
+    """every model call writes its slices [s, e) of the plane's preallocated heads: with 30 720 pixels per call the planes
+    take 14, 15 and 18 calls of 3, 5 and 5 slices, the last one of 1, 2 and 3 -- the offset of a batch and the short
+    tail -- and the volumes equal those of the default batch_pixels (one call per plane)"""
+    from empanada_amd.data import DeviceVolume
+    from empanada_amd.inference.driver import infer_volume, slices_per_call
+    vol = SY.em_volume((40, 72, 88), seed=3)
+    engine = _engine(ks=3, render=render)
+    dv = DeviceVolume(vol, NORMS['mean'], NORMS['std'], 32, 'cuda')
+    small = 5 * 64 * 96
+    for axis, per in (('xy', 3), ('xz', 5), ('yz', 5)):
+        n = dv.n_slices(axis)
+        assert slices_per_call(dv, axis, small) == per and n >= 3 * per and n % per
+        assert slices_per_call(dv, axis, 32 << 20) >= n
+    kw = dict(norms=NORMS, labels=[1, 2], min_size=30, min_span=2)
+    exp = infer_volume(engine, dv, **kw)
+    got = infer_volume(engine, dv, batch_pixels=small, **kw)
+    assert got['instances'] == exp['instances'] and got['z_range'] == exp['z_range'] == (0, 40)
+    for c in (1, 2):
+        assert torch.equal(got['volumes'][c].view(torch.uint8), exp['volumes'][c].view(torch.uint8)), f'class {c}'
+    assert int(exp['volumes'][1].view(torch.int32).max()) > 0 or int(exp['volumes'][2].max()) > 0
