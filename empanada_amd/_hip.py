@@ -108,6 +108,10 @@ SIGNATURES = {
     'emp_fill_runs_u8': (_I, [_P, _L, _P, _P, _L, _c.c_uint8, _P]),
     'emp_triplets_reduce_work_bytes': (_L, [_L]),
     'emp_triplets_reduce': (_I, [_P, _L, _P, _L, _P, _P, _P]),
+    'emp_label_overlaps_count_work_bytes': (_L, [_L]),
+    'emp_label_overlaps_count': (_I, [_P, _I, _P, _I, _L, _L, _P, _L, _P, _P]),
+    'emp_label_overlaps_work_bytes': (_L, [_L]),
+    'emp_label_overlaps': (_I, [_P, _I, _P, _I, _L, _L, _P, _L, _P, _L, _P, _P, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -171,6 +175,9 @@ def np_to_dev_u32(a):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+_current_stream = stream     # for wrappers that take a `stream` argument of their own
 
 
 # optional per-call HIP-event timing (bench.py): name -> list of (start_event, end_event, algorithmic bytes or
@@ -491,6 +498,81 @@ def reduce_triplets(trip):
     cnt = torch.zeros((1,), dtype=torch.int32, device=dev)
     call('emp_triplets_reduce', _ptr(trip.contiguous()), n, _ptr(work), wb, _ptr(out), _ptr(cnt), stream())
     return out[:int(cnt.item())]
+
+
+OVERLAP_MAX_VOXELS = 2 ** 31 - 1     # voxels per emp_label_overlaps call: one span per voxel must fit the int32 scan
+
+
+def _overlap_operand(what, t):
+    _expect(f"label_overlaps: {what}", t, (torch.uint8, torch.int32, torch.uint32))
+    if not t.is_contiguous():
+        raise HipError(f"label_overlaps: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    return t, (1 if t.dtype == torch.uint8 else 4)
+
+
+def label_overlaps(gt, pred, stream=None, info=None):
+    """Sparse overlap table of two label arrays of equal shape (any rank; the last axis is the contiguous one), each
+    uint8 or int32 / uint32 (read as uint32), on the same device and contiguous: (pairs (n, 2) int64, counts (n,) int64)
+    on that device, one row per distinct (gt label, pred label) != (0, 0) that occurs, ascending by (gt, pred); rows
+    with one side 0 are included.  Exact and the same from run to run.  stream: a torch.cuda.Stream to run on instead of
+    the current one.  An array of more than OVERLAP_MAX_VOXELS voxels goes through the kernel in blocks of rows, the
+    tables are added.  Two host syncs per block (span count, pair count).  info: a dict that receives 'blocks' (kernel
+    calls made), 'spans' (spans of constant pair they sorted) and 'work_bytes' (largest workspace of one call)."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return label_overlaps(gt, pred, info=info)
+    require_gpu()
+    gt, gb = _overlap_operand("gt", gt)
+    pred, pb = _overlap_operand("pred", pred)
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"label_overlaps: gt is {tuple(gt.shape)}, pred {tuple(pred.shape)}")
+    if gt.device != pred.device:
+        raise HipError(f"label_overlaps: gt is on {gt.device}, pred on {pred.device}")
+    dev = gt.device
+    empty = (torch.zeros((0, 2), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev))
+    stats = {'blocks': 0, 'spans': 0, 'work_bytes': 0} if info is None else info
+    stats.update(blocks=0, spans=0, work_bytes=0)
+    if gt.numel() == 0:
+        return empty
+    W = int(gt.shape[-1]) if gt.dim() else 1
+    if W > OVERLAP_MAX_VOXELS:
+        raise ValueError(f"label_overlaps: a contiguous extent of {W} voxels exceeds {OVERLAP_MAX_VOXELS}; reshape the "
+                         "arrays into shorter rows")
+    g2, p2 = gt.reshape(-1, W), pred.reshape(-1, W)
+    R = int(g2.shape[0])
+    block = max(1, OVERLAP_MAX_VOXELS // W)
+    tables = []
+    with torch.cuda.device(dev):
+        for r0 in range(0, R, block):
+            g, p = g2[r0:r0 + block], p2[r0:r0 + block]
+            rows = int(g.shape[0])
+            wb = query('emp_label_overlaps_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_overlaps_count', _ptr(g), gb, _ptr(p), pb, rows, W, _ptr(work), wb, _ptr(offs),
+                 _current_stream(), alg_bytes=rows * W * (gb + pb))
+            n_spans = int(offs[-1].item())
+            stats['blocks'] += 1
+            stats['spans'] += n_spans
+            if n_spans == 0:
+                continue
+            wb = query('emp_label_overlaps_work_bytes', n_spans)
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            pairs = torch.empty((n_spans, 2), dtype=torch.int64, device=dev)
+            counts = torch.empty((n_spans,), dtype=torch.int64, device=dev)
+            n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_overlaps', _ptr(g), gb, _ptr(p), pb, rows, W, _ptr(offs), n_spans, _ptr(work), wb,
+                 _ptr(pairs), _ptr(counts), _ptr(n_out), _current_stream(), alg_bytes=rows * W * (gb + pb))
+            n = int(n_out.item())
+            # the capacity is one row per span: keep the table only
+            tables.append((pairs[:n].clone(), counts[:n].clone()))
+    if not tables:
+        return empty
+    if len(tables) == 1:
+        return tables[0]
+    from .evaluation import merge_overlaps
+    return merge_overlaps(tables)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -3,12 +3,18 @@
 Formula: empanada/evaluation/panoptic_metrics.py:3-54; matching: Hungarian on the instance IoU matrix with the
 matches kept at IoU >= 0.5 (empanada/evaluation/evaluator.py:88-89 -> rle_matcher, inference/matcher.py:136-232).
 The IoU table comes from one joint histogram of (gt label, pred label) over the voxels.
+
+Two routes to that histogram: `volume_pq` builds it densely with library calls (small volumes, and the independent check
+of the other route); `volume_scores` reads it as a SPARSE table of (gt label, pred label, voxels) from
+_hip.label_overlaps (csrc/emp_overlaps.hip) slab by slab, rank by rank, and scores it with `scores_from_overlaps`:
+IoU, F1 / precision / recall at 0.5 and 0.75 and PQ, what scripts/evaluate3d.py:204-218 prints per class.
 """
 import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 
-__all__ = ['panoptic_quality', 'volume_pq', 'f1', 'ap', 'precision', 'recall', 'f1_50', 'f1_75', 'precision_50',
+__all__ = ['panoptic_quality', 'volume_pq', 'merge_overlaps', 'gather_overlaps', 'scores_from_overlaps', 'volume_overlaps',
+           'volume_scores', 'f1', 'ap', 'precision', 'recall', 'f1_50', 'f1_75', 'precision_50',
            'precision_75', 'recall_50', 'recall_75', 'iou', 'Evaluator']
 
 
@@ -179,3 +185,214 @@ class Evaluator:
             return results, dict(gt_matched=gt_matched, pred_matched=pred_matched, gt_unmatched=gt_unmatched,
                                  pred_unmatched=pred_unmatched, matched_ious=matched_ious)
         return results
+
+
+# ----------------------------------------------------------------------------- scores from the sparse overlap table
+def _is_torch(tables):
+    return any(isinstance(x, torch.Tensor) for t in tables for x in t)
+
+
+def merge_overlaps(tables):
+    """Sum of overlap tables: `tables` is a sequence of (pairs (n, 2), counts (n,)) -- of a volume's slabs, of the
+    ranks' shares -- and the result is one such table with every distinct pair once, its counts added, ascending by
+    (gt label, pred label).  numpy in, numpy out; with any torch tensor among them the result is a torch table on that
+    tensor's device.  Integer sums: exact whatever the order."""
+    tables = [(p, c) for p, c in tables]
+    if _is_torch(tables):
+        dev = next(x.device for t in tables for x in t if isinstance(x, torch.Tensor))
+        pairs = [torch.as_tensor(p).to(dev).reshape(-1, 2).long() for p, _ in tables]
+        counts = [torch.as_tensor(c).to(dev).reshape(-1).long() for _, c in tables]
+        pairs = torch.cat(pairs) if pairs else torch.zeros((0, 2), dtype=torch.int64, device=dev)
+        counts = torch.cat(counts) if counts else torch.zeros((0,), dtype=torch.int64, device=dev)
+        if pairs.shape[0] == 0:
+            return pairs, counts
+        uniq, inv = torch.unique(pairs, dim=0, return_inverse=True)      # rows in lexicographic order
+        return uniq, torch.zeros((uniq.shape[0],), dtype=torch.int64, device=dev).index_add_(0, inv.reshape(-1), counts)
+    pairs = [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p, _ in tables]
+    counts = [np.asarray(c, dtype=np.int64).reshape(-1) for _, c in tables]
+    pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int64)
+    counts = np.concatenate(counts) if counts else np.zeros((0,), np.int64)
+    if len(pairs) == 0:
+        return pairs, counts
+    order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+    pairs, counts = pairs[order], counts[order]
+    head = np.concatenate([[True], np.any(pairs[1:] != pairs[:-1], axis=1)])
+    return pairs[head], np.add.reduceat(counts, np.flatnonzero(head))
+
+
+def gather_overlaps(pairs, counts, group=None):
+    """The ranks' overlap tables added up: every rank of `group` passes its own table and receives the table of all of
+    them (one count all-gather + one padded all-gather, as the run tables travel in inference/sharded.py).  Without an
+    initialised process group the table comes back merged with itself, i.e. sorted."""
+    from .inference import sharded
+    if sharded._world(group)[1] == 1:
+        return merge_overlaps([(pairs, counts)])
+    was_numpy = not isinstance(pairs, torch.Tensor)
+    p = torch.as_tensor(pairs).reshape(-1, 2).long()
+    c = torch.as_tensor(counts).reshape(-1).long().to(p.device)
+    parts = sharded._gather_var(torch.cat([p, c[:, None]], dim=1), group)
+    pairs, counts = merge_overlaps([(t[:, :2], t[:, 2]) for t in parts])
+    return (pairs.cpu().numpy(), counts.cpu().numpy()) if was_numpy else (pairs, counts)
+
+
+def _match_components(gi, pi, iou, n_g):
+    """Maximum-IoU assignment on the bipartite graph of the pairs with a positive intersection, one connected component
+    at a time: edges (gi[k], pi[k]) with weight iou[k] > 0.  Pairs that do not intersect have IoU 0 and add nothing to
+    the optimum, so this is the assignment of the dense matrix wherever that optimum is unique.  Returns the indices k
+    of the chosen edges."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    if len(gi) == 0:
+        return np.zeros(0, np.int64)
+    n = n_g + int(pi.max()) + 1
+    graph = coo_matrix((np.ones(len(gi), np.int8), (gi, n_g + pi)), shape=(n, n))
+    comp = connected_components(graph, directed=False)[1][gi]
+    order = np.argsort(comp, kind='stable')
+    bounds = np.flatnonzero(np.concatenate([[True], comp[order][1:] != comp[order][:-1], [True]]))
+    single = np.diff(bounds) == 1
+    chosen = [order[bounds[:-1][single]]]                               # an edge alone in its component is the match
+    for lo, hi in zip(bounds[:-1][~single], bounds[1:][~single]):
+        e = order[lo:hi]
+        gu, gr = np.unique(gi[e], return_inverse=True)
+        pu, pc = np.unique(pi[e], return_inverse=True)
+        block = np.zeros((len(gu), len(pu)), dtype=np.float64)
+        block[gr, pc] = iou[e]
+        slot = np.full(block.shape, -1, dtype=np.int64)
+        slot[gr, pc] = e
+        rows, cols = linear_sum_assignment(block, maximize=True)
+        k = slot[rows, cols]
+        chosen.append(k[k >= 0])                                        # a zero entry is no pair at all
+    return np.sort(np.concatenate(chosen))
+
+
+def scores_from_overlaps(pairs, counts, iou_thr=0.5, instances=True, return_instances=False):
+    """Scores of a predicted label volume against the ground truth from their overlap table alone: `pairs` (n, 2) the
+    distinct (gt label, pred label) != (0, 0) with `counts` (n,) voxels each, as _hip.label_overlaps / merge_overlaps
+    give them (numpy or torch).  No GPU is needed.
+
+    The area of a label is its row (column) sum, IoU is formed only for the pairs that intersect, and the assignment
+    that maximises the total IoU is solved per connected component of those pairs; matches with IoU >= iou_thr
+    (> 0) are kept -- what rle_matcher does on the dense IoU matrix (inference/matcher.py:48-52), and the same result
+    whenever that optimum is unique.  The match then goes through this module's metric functions, so the numbers follow
+    the Evaluator's rules (f1_75 counts a match below 0.75 as one false positive and one false negative, PQ does the
+    same below 0.5).
+
+    Returns {'IoU', 'F1_50', 'F1_75', 'Precision_50', 'Precision_75', 'Recall_50', 'Recall_75', 'PQ', 'n_gt',
+    'n_pred', 'n_matched'}; with instances=False (stuff classes) {'IoU'} alone.  'IoU' is that of the two foreground
+    masks: voxels where both are non-zero over voxels where either is, 1 when both volumes are empty and 0 when one is.
+    The reference's Evaluator scores a class with fewer than two predicted instances as the run table [[-1, -1]]
+    (evaluation/evaluator.py:6-22), an accident of its run merging; that is not reproduced here: one predicted
+    instance is scored like any other number.  With return_instances the match itself is returned as well:
+    (scores, {'gt_matched', 'gt_unmatched', 'pred_matched', 'pred_unmatched', 'matched_ious'})."""
+    if isinstance(pairs, torch.Tensor):
+        pairs = pairs.cpu().numpy()
+    if isinstance(counts, torch.Tensor):
+        counts = counts.cpu().numpy()
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if len(pairs) != len(counts):
+        raise ValueError(f"scores_from_overlaps: {len(pairs)} pairs, {len(counts)} counts")
+    if not iou_thr > 0:
+        raise ValueError(f"scores_from_overlaps: iou_thr must be > 0 (got {iou_thr}): pairs that do not intersect are "
+                         "not in the table")
+    g, p = pairs[:, 0], pairs[:, 1]
+    both = int(counts[(g > 0) & (p > 0)].sum())
+    either = int(counts[(g > 0) | (p > 0)].sum())
+    scores = {'IoU': 1.0 if either == 0 else both / either}
+    if not instances:
+        return (scores, None) if return_instances else scores
+    gl, g_idx = np.unique(g[g > 0], return_inverse=True)
+    pl, p_idx = np.unique(p[p > 0], return_inverse=True)
+    ga = np.zeros(len(gl), np.int64)
+    pa = np.zeros(len(pl), np.int64)
+    np.add.at(ga, g_idx.reshape(-1), counts[g > 0])
+    np.add.at(pa, p_idx.reshape(-1), counts[p > 0])
+    edge = (g > 0) & (p > 0)
+    gi = np.searchsorted(gl, g[edge])
+    pi = np.searchsorted(pl, p[edge])
+    inter = counts[edge].astype(np.float64)
+    iou_e = inter / (ga[gi].astype(np.float64) + pa[pi].astype(np.float64) - inter)
+    k = _match_components(gi, pi, iou_e, len(gl))
+    k = k[iou_e[k] >= iou_thr]
+    match = dict(gt_matched=gl[gi[k]], gt_unmatched=np.setdiff1d(gl, gl[gi[k]]), pred_matched=pl[pi[k]],
+                 pred_unmatched=np.setdiff1d(pl, pl[pi[k]]), matched_ious=iou_e[k])
+    scores.update(F1_50=float(f1_50(**match)), F1_75=float(f1_75(**match)),
+                  Precision_50=float(precision_50(**match)), Precision_75=float(precision_75(**match)),
+                  Recall_50=float(recall_50(**match)), Recall_75=float(recall_75(**match)),
+                  PQ=float(panoptic_quality(**match)), n_gt=len(gl), n_pred=len(pl), n_matched=int(len(k)))
+    return (scores, match) if return_instances else scores
+
+
+_SLAB_VOXELS = 1 << 27        # host volumes are uploaded in slabs of about this many voxels (512 MiB of uint32)
+
+
+def _labels_to_device(x, dev):
+    """one slab of labels as a contiguous uint8 or uint32 tensor on `dev`; any integer type whose values fit 32 bits"""
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bool:
+            x = x.to(torch.uint8)
+        if x.dtype not in (torch.uint8, torch.int32, torch.uint32):
+            if x.is_floating_point() or x.is_complex():
+                raise ValueError(f"volume_scores: labels must be integers, got {x.dtype}")
+            x = x.to(torch.int64)
+            if x.numel() and (int(x.min()) < 0 or int(x.max()) >= 2 ** 32):
+                raise ValueError("volume_scores: labels must lie in 0 .. 2^32 - 1")
+            x = x.to(torch.int32)                                       # keeps the low 32 bits
+        return x.to(dev).contiguous()
+    a = np.asarray(x)
+    if a.dtype == np.bool_:
+        a = a.astype(np.uint8)
+    if a.dtype.kind not in 'iu':
+        raise ValueError(f"volume_scores: labels must be integers, got {a.dtype}")
+    if a.dtype == np.uint8:
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if a.dtype != np.uint32:
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
+            raise ValueError("volume_scores: labels must lie in 0 .. 2^32 - 1")
+        a = a.astype(np.uint32)
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(dev).view(torch.uint32)
+
+
+def volume_overlaps(gt, pred, *, slab_rows=None, group=None):
+    """The overlap table of two label volumes of equal shape as a numpy (pairs, counts): `gt` and `pred` are numpy
+    arrays, tensors or anything that has a shape and can be sliced along axis 0 (a ZarrV2Array, say).  Every slab of
+    slab_rows indices along axis 0 goes to the device (host data is uploaded slab by slab, so neither volume has to be
+    resident as a whole) and through _hip.label_overlaps, and the tables are added; slab_rows=None takes device tensors
+    whole and host data in slabs of about 2^27 voxels.  With `group` the ranks' tables are added too: every rank passes
+    its own share of the volume and all receive the table of the whole."""
+    from . import _hip
+    _hip.require_gpu()
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"volume_scores: gt is {tuple(gt.shape)}, pred {tuple(pred.shape)}")
+    if len(gt.shape) < 1:
+        raise ValueError("volume_scores: the volumes need at least one axis")
+    on_dev = [x.device for x in (gt, pred) if isinstance(x, torch.Tensor) and x.is_cuda]
+    if len(set(on_dev)) > 1:
+        raise ValueError(f"volume_scores: gt and pred are on different devices ({on_dev[0]}, {on_dev[1]})")
+    dev = on_dev[0] if on_dev else torch.device('cuda', torch.cuda.current_device())
+    n = int(gt.shape[0])
+    if slab_rows is None:
+        per_row = int(np.prod(gt.shape[1:], dtype=np.int64))
+        slab_rows = max(n, 1) if len(on_dev) == 2 else max(1, _SLAB_VOXELS // max(per_row, 1))
+    elif isinstance(slab_rows, bool) or not isinstance(slab_rows, (int, np.integer)) or slab_rows < 1:
+        raise ValueError(f"volume_scores: slab_rows must be a positive number of indices along axis 0, got {slab_rows!r}")
+    tables = []
+    for z in range(0, n, int(slab_rows)):
+        g = _labels_to_device(gt[z:z + slab_rows], dev)
+        p = _labels_to_device(pred[z:z + slab_rows], dev)
+        tables.append(_hip.label_overlaps(g, p))
+        del g, p
+    if tables:
+        pairs, counts = merge_overlaps(tables)
+    else:
+        pairs, counts = torch.zeros((0, 2), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev)
+    pairs, counts = gather_overlaps(pairs, counts, group)
+    return pairs.cpu().numpy(), counts.cpu().numpy()
+
+
+def volume_scores(gt, pred, *, instances=True, iou_thr=0.5, slab_rows=None, group=None):
+    """scores_from_overlaps of two label volumes of equal shape (see there for what is returned): the table is read on
+    the device by volume_overlaps -- slab by slab for host data, nothing widened, and added over the ranks of `group`,
+    each of which passes its own share and receives the scores of the whole."""
+    pairs, counts = volume_overlaps(gt, pred, slab_rows=slab_rows, group=group)
+    return scores_from_overlaps(pairs, counts, iou_thr=iou_thr, instances=instances)

@@ -157,6 +157,28 @@ def _check_windows(window_slices, mem_budget, pipeline, world):
     return w if w is None or w == 'auto' else int(w)
 
 
+def _check_ground_truth(ground_truth, labels, shape3d):
+    """argument errors of the scoring, before any GPU work"""
+    if ground_truth is None:
+        return
+    for c, gt in ground_truth.items():
+        if c not in labels:
+            raise ValueError(f"ground_truth has class {c!r}, the labels are {labels}")
+        if tuple(gt.shape) != tuple(shape3d):
+            raise ValueError(f"ground_truth[{c!r}] is {tuple(gt.shape)}, the volume {tuple(shape3d)}")
+
+
+def _scored(res, ground_truth, thing_list, group):
+    """the result with 'scores': each rank's slab of every class that has a ground truth against the same z-range of
+    it, the overlap tables added over the ranks"""
+    if ground_truth is not None:
+        from ..evaluation import volume_scores
+        z0, z1 = res['z_range']
+        res['scores'] = {c: volume_scores(gt[z0:z1], res['volumes'][c], instances=c in thing_list, group=group)
+                         for c, gt in ground_truth.items()}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -183,7 +205,7 @@ def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, win
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
-                 window_slices=None, mem_budget=None):
+                 window_slices=None, mem_budget=None, ground_truth=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -204,6 +226,12 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     the volumes are the same.  W is rounded down to a multiple of the slices per model call; 'auto' takes the whole
     plane when it fits into mem_budget bytes (None: the free device memory) and the largest window that does otherwise.
     The result gains 'windows': {axis: steps} and 'head_bytes': bytes of head buffers held.  Not with several ranks.
+    ground_truth: {class: (D, H, W) integer labels} for any of `labels` (numpy array, tensor, or anything sliceable along
+    z such as a zarr array): once the volumes exist every rank scores its z-slab against the same slab of the ground
+    truth (evaluation.volume_scores: overlap table on the device, added over the ranks) and the result gains
+    'scores': {class: {'IoU', 'F1_50', 'F1_75', 'Precision_50', 'Precision_75', 'Recall_50', 'Recall_75', 'PQ', 'n_gt',
+    'n_pred', 'n_matched'}} for thing classes and {'IoU'} for stuff classes -- the numbers scripts/evaluate3d.py:204-218
+    prints.  None: no new key, nothing else changes.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -232,6 +260,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         dv = DeviceVolume(volume, norms['mean'], norms['std'], factor, next(engine.model.parameters()).device, scale=f)
     steps = render_steps + f.bit_length() - 1
     shape3d = dv.shape
+    _check_ground_truth(ground_truth, labels, shape3d)
     params = dict(thing_list=thing_list, label_divisor=div, stuff_area=engine.stuff_area, void_label=engine.void_label,
                   nms_threshold=engine.nms_threshold, nms_kernel=engine.nms_kernel,
                   confidence_thr=engine.confidence_thr, median_kernel_size=getattr(engine, 'ks', 1),
@@ -254,8 +283,9 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         return vols, zs, {c: int(cons[c].alive.sum()) for c in labels}
 
     if pipeline is not None:
-        return pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
-                            track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices)
+        res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
+                           track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices)
+        return _scored(res, ground_truth, thing_list, group)
     planes, base = {}, 0
     windows = {'windows': {}, 'head_bytes': 0}
     for axis in axes:
@@ -276,4 +306,5 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     if out is not None:
         for c in labels:
             datasets[c].write_slab(z0, host_slab(vols[c], c in thing_list))
-    return result(vols, (z0, z1), counts, datasets, **(windows if window_slices is not None else {}))
+    return _scored(result(vols, (z0, z1), counts, datasets, **(windows if window_slices is not None else {})),
+                   ground_truth, thing_list, group)

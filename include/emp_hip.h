@@ -599,6 +599,32 @@ int64_t emp_triplets_reduce_work_bytes(int64_t n);
 int emp_triplets_reduce(const int32_t *triplets, int64_t n, void *work, int64_t work_bytes, int32_t *out,
                         int32_t *n_out, void *stream);
 
+/* ---- E1: sparse overlap table of two label volumes (ground truth against prediction) --------------------------
+ * replaces the instance IoU matrix of Evaluator.__call__   empanada/evaluation/evaluator.py:88-89
+ *          rle_matcher                                      empanada/inference/matcher.py:136-232
+ *          as input of panoptic_quality                     empanada/evaluation/panoptic_metrics.py:3-54
+ *          and of the scores scripts/evaluate3d.py:204-218 prints
+ * gt and pred are label arrays of equal shape (R, W), W contiguous; each is uint8 (gt_bytes / pred_bytes = 1) or
+ * uint32 (4), read as they are.  The result is every distinct pair (g, p) != (0, 0) that occurs with its voxel count,
+ * ascending by (g, p) as unsigned numbers; pairs with one side 0 are included, so the area of a label is a row or
+ * column sum.  Counts are integer sums: exact, and the same from run to run.
+ * Step 1  emp_label_overlaps_count: row_offsets[0..R] (R+1 int32) = exclusive prefix sum of the number of maximal
+ *         spans of constant pair != (0, 0) per row; row_offsets[R] is the span total n_spans, which sizes step 2
+ *         exactly.  work: emp_label_overlaps_count_work_bytes(R) bytes.
+ * Step 2  emp_label_overlaps: spans -> (key = g << 32 | p, length) -> sort -> sum of equal keys.  out_pairs
+ *         (n_spans, 2) int64 and out_counts (n_spans) int64 receive n_out (device int32[1]) rows; the labels must not
+ *         have changed since step 1.  work: emp_label_overlaps_work_bytes(n_spans) bytes.
+ * A call covers at most 2^31 - 1 voxels (R * W; one span per voxel is the worst case and the scan is int32): a larger
+ * array is refused with EMP_EINVAL, never truncated -- callers split the rows into blocks and add the tables
+ * (_hip.label_overlaps does).  Per voxel each step reads gt_bytes + pred_bytes bytes; all else is O(n_spans).      */
+int64_t emp_label_overlaps_count_work_bytes(int64_t R);
+int emp_label_overlaps_count(const void *gt, int gt_bytes, const void *pred, int pred_bytes, int64_t R, int64_t W,
+                             void *work, int64_t work_bytes, int32_t *row_offsets, void *stream);
+int64_t emp_label_overlaps_work_bytes(int64_t n_spans);
+int emp_label_overlaps(const void *gt, int gt_bytes, const void *pred, int pred_bytes, int64_t R, int64_t W,
+                       const int32_t *row_offsets, int64_t n_spans, void *work, int64_t work_bytes,
+                       int64_t *out_pairs, int64_t *out_counts, int32_t *n_out, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
