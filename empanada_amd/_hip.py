@@ -112,6 +112,10 @@ SIGNATURES = {
     'emp_label_overlaps_count': (_I, [_P, _I, _P, _I, _L, _L, _P, _L, _P, _P]),
     'emp_label_overlaps_work_bytes': (_L, [_L]),
     'emp_label_overlaps': (_I, [_P, _I, _P, _I, _L, _L, _P, _L, _P, _L, _P, _P, _P, _P]),
+    'emp_deflate_bound': (_L, [_L, _I]),
+    'emp_deflate_work_bytes': (_L, [_L, _L, _I]),
+    'emp_deflate_count': (_I, [_P, _I, _L, _L, _P, _L, _P, _P]),
+    'emp_deflate_encode': (_I, [_P, _I, _L, _L, _P, _L, _L, _P, _L, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -573,6 +577,72 @@ def label_overlaps(gt, pred, stream=None, info=None):
         return tables[0]
     from .evaluation import merge_overlaps
     return merge_overlaps(tables)
+
+
+DEFLATE_MAX_BYTES = 2 ** 31 - 1      # worst-case output of one emp_deflate_count call: its segment sizes are scanned in int32
+
+
+def deflate_bound(chunk_bytes, item):
+    """most bytes the zlib stream of one chunk of `chunk_bytes` raw bytes (elements of `item` = 1 or 4 bytes) can take:
+    2 + ceil(9 L / 8) + 8 ceil(L / 4096) + 6 (include/emp_hip.h, Z1)"""
+    n = int(query('emp_deflate_bound', int(chunk_bytes), int(item)))
+    if n < 0:
+        raise ValueError(f"deflate_bound: {load().emp_last_error().decode()}")
+    return n
+
+
+def deflate_labels(slab, out=None):
+    """One zlib stream per slice of a label slab, made on the device (emp_deflate_count / emp_deflate_encode; the format
+    is in include/emp_hip.h, Z1, and any inflate reads it).  slab: (n, Y, X), contiguous, on the GPU, uint8 or int32 /
+    uint32 (the bits are taken as they are).  Returns (data, offsets): offsets is a host int64 tensor of n + 1 entries,
+    chunk i is data[offsets[i]:offsets[i + 1]]; data is a uint8 device tensor of exactly offsets[-1] bytes -- the first
+    offsets[-1] bytes of `out` when a 1-d contiguous uint8 device tensor is passed (n * deflate_bound(Y * X * item, item)
+    bytes always suffice; one that turns out too short is a ValueError, and bytes past offsets[-1] are never written).
+    A slab whose worst case exceeds DEFLATE_MAX_BYTES goes through the kernels in blocks of slices.  One host sync per
+    block (its byte total)."""
+    require_gpu()
+    _expect("deflate_labels: slab", slab, (torch.uint8, torch.int32, torch.uint32))
+    if slab.dim() != 3 or not slab.is_contiguous():
+        raise HipError(f"deflate_labels: slab must be a contiguous (n, Y, X) tensor, got {tuple(slab.shape)} with strides "
+                       f"{tuple(slab.stride())}")
+    item = 1 if slab.dtype == torch.uint8 else 4
+    n, L = int(slab.shape[0]), int(slab.shape[1]) * int(slab.shape[2]) * item
+    dev = slab.device
+    if out is not None:
+        _expect("deflate_labels: out", out, torch.uint8)
+        if out.dim() != 1 or not out.is_contiguous() or out.device != dev:
+            raise HipError(f"deflate_labels: out must be a contiguous 1-d uint8 tensor on {dev}")
+    if n == 0 or L == 0:
+        data = torch.empty((0,), dtype=torch.uint8, device=dev) if out is None else out[:0]
+        return data, torch.zeros((n + 1,), dtype=torch.int64)
+    bound = deflate_bound(L, item)
+    if bound > DEFLATE_MAX_BYTES:
+        raise ValueError(f"deflate_labels: a slice of {L} bytes could take more than {DEFLATE_MAX_BYTES} compressed")
+    block = max(1, DEFLATE_MAX_BYTES // bound)
+    counted, offsets, at = [], [torch.zeros((1,), dtype=torch.int64)], 0
+    with torch.cuda.device(dev):
+        for c0 in range(0, n, block):
+            part = slab[c0:c0 + block]
+            m = int(part.shape[0])
+            wb = int(query('emp_deflate_work_bytes', m, L, item))
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((m + 1,), dtype=torch.int64, device=dev)
+            call('emp_deflate_count', _ptr(part), item, m, L, _ptr(work), wb, _ptr(offs), _current_stream(),
+                 alg_bytes=m * L)
+            offs = offs.cpu()                                   # the sync: this block's byte total
+            counted.append((part, m, work, wb, at, int(offs[-1])))
+            offsets.append(offs[1:] + at)
+            at += int(offs[-1])
+        if out is None:
+            data = torch.empty((at,), dtype=torch.uint8, device=dev)
+        elif out.numel() < at:
+            raise ValueError(f"deflate_labels: out holds {out.numel()} bytes, the streams take {at}")
+        else:
+            data = out[:at]
+        for part, m, work, wb, base, total in counted:
+            call('emp_deflate_encode', _ptr(part), item, m, L, _ptr(work), wb, total, data.data_ptr() + base, total,
+                 _current_stream(), alg_bytes=m * L + total)
+    return data, torch.cat(offsets)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -20,6 +20,7 @@ import torch
 
 from .. import _hip
 from ..data import DeviceVolume
+from ..zarr_utils import ZarrV2Group
 from . import sharded, windowed
 from .engines import logits_to_prob
 
@@ -98,16 +99,18 @@ def forward_heads(model, margs, dv, axis, lo, hi, per, bufs, at=0):
                     {k: v[at + s - lo:at + e - lo] for k, v in bufs.items()})
 
 
-def open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group):
+def open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor=None):
     """{class: the '<class name>_pred' array of `out`, or None without one}: uint32 for thing classes, uint8 for stuff,
-    chunks (1, Y, X) (pdl_inference3d.py:225-233); rank 0 creates them before any rank opens one"""
+    chunks (1, Y, X) (pdl_inference3d.py:225-233); rank 0 creates them before any rank opens one.  compressor='zlib':
+    created with {"id": "zlib", "level": 1} (the reference's datasets are compressed too, :228-233)"""
     if out is None:
         return {c: None for c in labels}
     names = {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}
+    extra = {} if compressor is None else {'compressor': {'id': 'zlib', 'level': 1}}
     if rank == 0:
         for c in labels:
             out.create_dataset(names[c], shape=shape3d, dtype=np.uint32 if c in thing_list else np.uint8,
-                               overwrite=True, chunks=(1, None, None))
+                               overwrite=True, chunks=(1, None, None), **extra)
     if world > 1:
         torch.distributed.barrier(group=group)
     return {c: out[names[c]] for c in labels}
@@ -118,9 +121,12 @@ def host_slab(vol, thing):
     return vol.view(torch.int32).cpu().numpy().view(np.uint32) if thing else vol.cpu().numpy()
 
 
-def result(vols, z_range, counts, datasets, windows=None, head_bytes=0, pipeline=None):
-    """infer_volume's result; windows ({axis: steps}): a windowed call, which also reports the head buffers it held"""
+def result(vols, z_range, counts, datasets, windows=None, head_bytes=0, pipeline=None, compressed=None):
+    """infer_volume's result; windows ({axis: steps}): a windowed call, which also reports the head buffers it held;
+    compressed ({class: bytes}): a call with compressor='zlib'"""
     res = {'volumes': vols, 'z_range': z_range, 'instances': counts, 'datasets': datasets}
+    if compressed is not None:
+        res['compressed_bytes'] = compressed
     if windows is not None:
         res.update(windows=windows, head_bytes=int(head_bytes))
     if pipeline is not None:
@@ -155,6 +161,19 @@ def _check_windows(window_slices, mem_budget, pipeline, world):
         raise ValueError(f"window_slices={w!r} with {world} ranks: windows within a rank's block are not built yet "
                          "(the hand-over across ranks stays as it is); leave window_slices=None")
     return w if w is None or w == 'auto' else int(w)
+
+
+def _check_compressor(compressor, out):
+    """argument errors of the compressed output, before any GPU work"""
+    if compressor is None:
+        return
+    if compressor != 'zlib':
+        raise ValueError(f"compressor must be None (raw chunks) or 'zlib', got {compressor!r}")
+    if out is None:
+        raise ValueError("compressor='zlib' without out=: there is nothing to compress, the volumes stay on the device")
+    if not isinstance(out, ZarrV2Group):
+        raise ValueError(f"compressor='zlib' needs out= to be a ZarrV2Group (the streams are written as its chunk files), "
+                         f"got {type(out).__name__}")
 
 
 def _check_ground_truth(ground_truth, labels, shape3d):
@@ -205,7 +224,7 @@ def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, win
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
-                 window_slices=None, mem_budget=None, ground_truth=None):
+                 window_slices=None, mem_budget=None, ground_truth=None, compressor=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -232,10 +251,15 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     'scores': {class: {'IoU', 'F1_50', 'F1_75', 'Precision_50', 'Precision_75', 'Recall_50', 'Recall_75', 'PQ', 'n_gt',
     'n_pred', 'n_matched'}} for thing classes and {'IoU'} for stuff classes -- the numbers scripts/evaluate3d.py:204-218
     prints.  None: no new key, nothing else changes.
+    compressor: None = the datasets hold raw chunks; 'zlib' = they are created with {"id": "zlib", "level": 1} and every
+    rank's slab of every class is made zlib streams on the device (ZarrV2Array.write_slab_device), so only compressed
+    bytes cross to the host and reach the disk, and no CPU compresses; needs out= to be a ZarrV2Group.  The result
+    gains 'compressed_bytes': {class: bytes this rank wrote}.  The volumes and what the datasets read back are the same.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
     window_slices = _check_windows(window_slices, mem_budget, pipeline, world)
+    _check_compressor(compressor, out)
     labels = list(labels)
     thing_list = list(engine.thing_list)
     div = engine.label_divisor
@@ -284,7 +308,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
-                           track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices)
+                           track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices,
+                           compressor=compressor)
         return _scored(res, ground_truth, thing_list, group)
     planes, base = {}, 0
     windows = {'windows': {}, 'head_bytes': 0}
@@ -302,9 +327,13 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         base += planes[axis].n_inst
         del pan
     vols, (z0, z1), counts = finish(planes)
-    datasets = open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group)
+    datasets = open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor)
+    compressed = None if compressor is None else {}
     if out is not None:
         for c in labels:
-            datasets[c].write_slab(z0, host_slab(vols[c], c in thing_list))
-    return _scored(result(vols, (z0, z1), counts, datasets, **(windows if window_slices is not None else {})),
-                   ground_truth, thing_list, group)
+            if compressor is None:
+                datasets[c].write_slab(z0, host_slab(vols[c], c in thing_list))
+            else:
+                compressed[c] = datasets[c].write_slab_device(z0, vols[c].contiguous())[1]
+    return _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed,
+                          **(windows if window_slices is not None else {})), ground_truth, thing_list, group)

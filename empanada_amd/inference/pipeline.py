@@ -15,7 +15,8 @@ What it changes against the plain call (driver._plane_heads + the serial plane l
   * overlap: forwards on one stream, everything downstream of a plane's forward on another, two sets of plane buffers;
     'auto' falls back to one set and serial planes when two planes' heads do not fit;
   * writing: the labelled slab goes to the zarr array through SlabWriter (pinned buffer, asynchronous copy, chunk files
-    written by a pool while the next class is copied).
+    written by a pool while the next class is copied); with infer_volume(..., compressor='zlib') the slab is made zlib
+    streams on the post stream first (ZarrV2Array.write_slab_device) and only those bytes are copied and written.
 With infer_volume(..., window_slices=) the planes stream through windows of slices (inference/windowed.py) and the two
 sets of buffers alternate per step of a plane instead of per plane (_run_windowed).
 What a plane is -- slices per model call, the model's arguments, head shapes, the loop that writes every batch's heads,
@@ -83,6 +84,8 @@ class VolumePipeline:
         self._streams = None
         self._store = [None, None]                    # flat fp32 storage of the two sets of plane buffers
         self._writers = {}
+        self._zpool = None                            # compressor='zlib': the writer threads ...
+        self._zbufs = {}                              # ... and one pinned buffer of compressed bytes per class
 
     # ------------------------------------------------------------------------------------------ checks, before GPU work
     def _param(self):
@@ -231,7 +234,7 @@ class VolumePipeline:
 
     # ------------------------------------------------------------------------------------------ the volume
     def run(self, dv, *, axes, labels, thing_list, params, steps, group, track, finish, class_names, out,
-            window_slices=None):
+            window_slices=None, compressor=None):
         """Called by infer_volume after its own argument checks.  track(pan, axis, base) and finish(planes) are the
         driver's own plane and volume steps, so both paths share them.  The loops over planes (_run_planes) or over the
         steps of every plane (_run_windowed, window_slices=) plan and allocate first and hand back their `walk`; all
@@ -264,7 +267,8 @@ class VolumePipeline:
         with self._deferring(), torch.cuda.stream(post):
             planes, windows, hist_bytes = walk(model, fwd, post)
             vols, (z0, z1), counts = finish(planes)
-            datasets = self._write(out, vols, z0, labels, thing_list, class_names, dv.shape, rank, world, group, post)
+            datasets, compressed = self._write(out, vols, z0, labels, thing_list, class_names, dv.shape, rank, world,
+                                               group, post, compressor)
         cur.wait_stream(post)
         cur.wait_stream(fwd)
         for v in vols.values():
@@ -274,7 +278,7 @@ class VolumePipeline:
         if windows is not None:
             pipe['windows'] = windows
         pipe['captures'] = (self._graphed.captures - captured) if graph else 0
-        return driver.result(vols, (z0, z1), counts, datasets, windows, head_bytes, pipe)
+        return driver.result(vols, (z0, z1), counts, datasets, windows, head_bytes, pipe, compressed)
 
     def _run_planes(self, dv, plan, shapes, margs, params, group, track, out_bytes):
         """Whole planes: the two sets of head buffers alternate per plane, the forward of plane i + 2 is queued as soon as
@@ -402,8 +406,33 @@ class VolumePipeline:
         w.retarget(array, z0)
         return w
 
-    def _write(self, out, vols, z0, labels, thing_list, class_names, shape3d, rank, world, group, post):
-        datasets = driver.open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group)
+    def _pinned(self, c, nbytes):
+        """class c's pinned buffer for compressed bytes: sized by what a slab actually took, and only ever grown"""
+        buf = self._zbufs.get(c)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._zbufs[c] = torch.empty((max(nbytes, 1),), dtype=torch.uint8).pin_memory()
+        return buf
+
+    def _write_compressed(self, datasets, vols, z0, labels):
+        """compressor='zlib': every class's slab is encoded on the post stream (the current one), its compressed bytes are
+        copied into the class's pinned buffer, and the chunk files are written by the pool while the next class is
+        encoded.  Returns {class: bytes written}"""
+        if self._zpool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._zpool = ThreadPoolExecutor(max_workers=4)
+        pending, compressed = [], {}
+        for c in labels:
+            futures, compressed[c] = datasets[c].write_slab_device(z0, vols[c].contiguous(), self._zpool,
+                                                                   host=lambda n, c=c: self._pinned(c, n))
+            pending += futures
+        for f in pending:
+            f.result()
+        return compressed
+
+    def _write(self, out, vols, z0, labels, thing_list, class_names, shape3d, rank, world, group, post, compressor=None):
+        datasets = driver.open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor)
+        if compressor is not None:
+            return datasets, self._write_compressed(datasets, vols, z0, labels)
         used = []
         for c in labels if out is not None else ():
             arr, thing = datasets[c], c in thing_list
@@ -417,9 +446,12 @@ class VolumePipeline:
                 arr.write_slab(z0, driver.host_slab(vols[c], thing))
         for w in used:
             w.drain()
-        return datasets
+        return datasets, None
 
     def close(self):
         for w in self._writers.values():
             w.close()
         self._writers = {}
+        if self._zpool is not None:
+            self._zpool.shutdown()
+        self._zpool, self._zbufs = None, {}

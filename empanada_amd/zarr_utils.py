@@ -152,7 +152,8 @@ class ZarrData:
 # `.zarray` JSON document per node and one file per chunk named by its dot-separated chunk index, C order,
 # little-endian, edge chunks padded to the full chunk shape with fill_value).  Compressor: none (raw bytes -- the
 # labelled slab goes from pinned memory to the file at memcpy speed) or stdlib zlib ({"id": "zlib"}, a numcodecs
-# codec every zarr reader has); stores compressed with the other numcodecs codecs the standard library covers (gzip,
+# codec every zarr reader has -- by zlib.compress on the host in write_chunk / write_slab, or as streams made on the
+# GPU in write_slab_device); stores compressed with the other numcodecs codecs the standard library covers (gzip,
 # bz2, lzma without filters) can be read and written too.  zarr's own default, Blosc, needs the blosc library and is not
 # produced here; files written by zarr with Blosc cannot be read here either (KeyError naming the codec).
 _CODECS = {
@@ -287,6 +288,61 @@ class ZarrV2Array:
                 self.write_chunk((z0 + i,) + tail, slab[i:i + 1])
             return []
         return [pool.submit(self.write_chunk, (z0 + i,) + tail, slab[i:i + 1]) for i in range(slab.shape[0])]
+
+    def _write_file(self, idx, raw):
+        with open(self._chunk_path(idx), 'wb') as fh:
+            fh.write(raw)
+
+    def check_slab_device(self, z0, device_slab):
+        """ValueError for what write_slab_device cannot write; touches neither the GPU nor the store"""
+        import torch
+        if self.codec != 'zlib':
+            raise ValueError(f"write_slab_device writes zlib streams: the array's compressor is {self.codec!r} "
+                             "(create it with compressor=1 or {'id': 'zlib', 'level': 1})")
+        if len(self.shape) != 3 or tuple(self.chunks) != (1,) + tuple(self.shape[1:]):
+            raise ValueError(f"write_slab_device needs a 3-d array with chunks (1, Y, X), got shape {self.shape} and "
+                             f"chunks {self.chunks}")
+        if self.dtype.itemsize not in (1, 4) or self.dtype.kind not in 'ui' or self.dtype.str[0] == '>':
+            raise ValueError(f"write_slab_device needs 1- or 4-byte little-endian integers, the array holds {self.dtype.str}")
+        if not isinstance(device_slab, torch.Tensor) or not device_slab.is_cuda:
+            raise ValueError("write_slab_device needs a tensor on the GPU (write_slab takes host arrays)")
+        item = {torch.uint8: 1, torch.int32: 4, torch.uint32: 4}.get(device_slab.dtype)
+        if item != self.dtype.itemsize:
+            raise ValueError(f"write_slab_device: a {device_slab.dtype} slab into an array of {self.dtype.str}")
+        if device_slab.dim() != 3 or tuple(device_slab.shape[1:]) != tuple(self.shape[1:]) or not device_slab.is_contiguous():
+            raise ValueError(f"write_slab_device needs a contiguous slab of whole slices (n, {self.shape[1]}, "
+                             f"{self.shape[2]}), got {tuple(device_slab.shape)}")
+        if z0 < 0 or z0 + device_slab.shape[0] > self.shape[0]:
+            raise ValueError(f"write_slab_device: slices {z0}..{z0 + device_slab.shape[0]} of {self.shape[0]}")
+
+    def write_slab_device(self, z0, device_slab, pool=None, host=None):
+        """write_slab for a slab that is still on the GPU, into an array compressed with zlib: every slice is made a
+        zlib stream on the device (_hip.deflate_labels -- no CPU compression, and only the compressed bytes cross to
+        the host), the streams are copied into a pinned buffer of their actual size and each chunk file is written
+        from its byte range, by `pool` when one is given.  host: a callable (nbytes) -> a pinned uint8 tensor of at
+        least nbytes to copy into instead of a new one; it must stay untouched until the futures are done.
+        Returns (futures, compressed bytes).  The files are what zlib.decompress and every zarr reader open."""
+        import torch
+        from . import _hip
+        z0 = int(z0)
+        self.check_slab_device(z0, device_slab)
+        if device_slab.numel() == 0:
+            return [], 0
+        data, offsets = _hip.deflate_labels(device_slab)
+        total = int(offsets[-1])
+        buf = host(total) if host is not None else torch.empty((total,), dtype=torch.uint8).pin_memory()
+        buf[:total].copy_(data, non_blocking=True)
+        torch.cuda.current_stream(device_slab.device).synchronize()
+        raw = memoryview(buf.numpy())
+        offsets = offsets.tolist()
+        futures = []
+        for i in range(device_slab.shape[0]):
+            part = raw[offsets[i]:offsets[i + 1]]
+            if pool is None:
+                self._write_file((z0 + i, 0, 0), part)
+            else:
+                futures.append(pool.submit(self._write_file, (z0 + i, 0, 0), part))
+        return futures, total
 
 
 class ZarrV2Group:

@@ -625,6 +625,39 @@ int emp_label_overlaps(const void *gt, int gt_bytes, const void *pred, int pred_
                        const int32_t *row_offsets, int64_t n_spans, void *work, int64_t work_bytes,
                        int64_t *out_pairs, int64_t *out_counts, int32_t *n_out, void *stream);
 
+/* ---- Z1: zlib streams of label slices, made on the device ----------------------------------------------------
+ * replaces zarr's default compressor behind zarr_store.create_dataset(...)   scripts/pdl_inference3d.py:228-233
+ *          (the reference stores its label volumes compressed, on the CPU)
+ * src is a slab of n_chunks slices of chunk_bytes = Y * X * item bytes each, C order, little endian, item = 1 (uint8)
+ * or 4 (uint32).  Every slice becomes one zlib stream (RFC 1950 / 1951) that any inflate decodes:
+ *     78 01 | seg_0 | seg_1 | ... | seg_{S-1} | 03 00 | adler32(raw), 4 bytes big-endian
+ * seg_k covers raw bytes [k * SEG, min(chunk_bytes, (k + 1) * SEG)), SEG = 4096.  Each segment is one fixed-Huffman
+ * block -- header bits 0,1,0 (BFINAL = 0, BTYPE = 01), the tokens, end-of-block (symbol 256) -- followed by an empty
+ * stored block: bits 0,0,0, zero bits up to the byte boundary, 00 00 FF FF.  So every segment ends byte-aligned and
+ * segments, and chunks, are concatenated as bytes.  03 00 is the empty final fixed block.
+ * Tokens, in element order: an element equal to the element before it in the chunk (also across a segment border,
+ * never across chunks: a chunk's first element is literal) is part of a repeat.  A maximal repeat of n bytes inside
+ * the segment is written as matches at distance `item` (distance code 0 or 3, five bits, no extra bits): length-258
+ * matches while n >= 261 or n == 258, then n = 259 / 260 as (n - 3, 3), then one match for 3 <= n <= 258; 1 or 2
+ * bytes (item 1 only) as literals.  Any other element is `item` literal bytes, 8 bits for values below 144 and 9
+ * for the rest.  Huffman codes are packed most significant bit first, extra bits least significant first.
+ * Worst case per chunk: emp_deflate_bound = 2 + ceil(9 L / 8) + 8 ceil(L / SEG) + 6 bytes, L = chunk_bytes.
+ * Step 1  emp_deflate_count: offsets[0..n_chunks] (device int64) = byte offset of every chunk's stream in the output;
+ *         offsets[n_chunks] is the total, which sizes step 2 exactly.  It also leaves the segment offsets and the
+ *         chunks' Adler-32 in `work` (emp_deflate_work_bytes bytes), which step 2 reads.
+ * Step 2  emp_deflate_encode: the streams, to out[0, total); nothing outside is written.  src and work must not have
+ *         changed since step 1 -- a segment whose size is no longer the counted one is left out, never overrun.
+ * A call's worst case (n_chunks * bound) must stay within 2^31 - 1 bytes (the segment sizes are scanned in int32): a
+ * larger slab is refused with EMP_EINVAL, callers split it into blocks of chunks (_hip.deflate_labels does).
+ * Per raw byte each step reads one byte; step 2 writes the compressed bytes; all else is per segment.
+ * The bound and the workspace query return -1 (and set emp_last_error) for arguments the steps would refuse.       */
+int64_t emp_deflate_bound(int64_t chunk_bytes, int item);
+int64_t emp_deflate_work_bytes(int64_t n_chunks, int64_t chunk_bytes, int item);
+int emp_deflate_count(const void *src, int item, int64_t n_chunks, int64_t chunk_bytes, void *work,
+                      int64_t work_bytes, int64_t *offsets, void *stream);
+int emp_deflate_encode(const void *src, int item, int64_t n_chunks, int64_t chunk_bytes, void *work,
+                       int64_t work_bytes, int64_t total, uint8_t *out, int64_t out_bytes, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
