@@ -116,6 +116,7 @@ SIGNATURES = {
     'emp_deflate_work_bytes': (_L, [_L, _L, _I]),
     'emp_deflate_count': (_I, [_P, _I, _L, _L, _P, _L, _P, _P]),
     'emp_deflate_encode': (_I, [_P, _I, _L, _L, _P, _L, _L, _P, _L, _P]),
+    'emp_label_pool_mode': (_I, [_P, _I, _L, _L, _L, _I, _I, _I, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -643,6 +644,57 @@ def deflate_labels(slab, out=None):
             call('emp_deflate_encode', _ptr(part), item, m, L, _ptr(work), wb, total, data.data_ptr() + base, total,
                  _current_stream(), alg_bytes=m * L + total)
     return data, torch.cat(offsets)
+
+
+def pooled_shape(shape, factors):
+    """shape of a (D, H, W) array pooled by `factors`: ceilings, the last cells are clipped"""
+    return tuple(-(-int(s) // int(f)) for s, f in zip(shape, factors))
+
+
+def pool_labels(slab, factors=(2, 2, 2), out=None):
+    """One level of a label pyramid (emp_label_pool_mode; the definition is in include/emp_hip.h, Z2): every voxel of
+    the result is the most frequent value of its fz x fy x fx cell of `slab`, clipped at the volume's end, the largest
+    unsigned value among equally frequent ones.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the
+    bits are taken as they are).  factors: three of 1 or 2, not all 1.  out: a contiguous tensor of the pooled shape,
+    the slab's dtype and device that does not overlap it.  Returns the pooled tensor (`out` when given), queued on the
+    current stream; no host sync.  ValueError for operands it cannot take, before anything is launched."""
+    try:
+        _expect("pool_labels: slab", slab, (torch.uint8, torch.int32, torch.uint32))
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if slab.dim() != 3 or not slab.is_contiguous():
+        raise ValueError(f"pool_labels: slab must be a contiguous (D, H, W) tensor, got {tuple(slab.shape)} with strides "
+                         f"{tuple(slab.stride())}")
+    import numbers
+    try:
+        f = tuple(factors)
+        ok = len(f) == 3 and all(not isinstance(v, bool) and isinstance(v, numbers.Integral) and v in (1, 2) for v in f)
+    except TypeError:
+        f, ok = (), False
+    if not ok or max(f) != 2:
+        raise ValueError(f"pool_labels: factors must be three of 1 or 2 with at least one 2, got {factors!r}")
+    f = tuple(int(v) for v in f)
+    shape = pooled_shape(slab.shape, f)
+    item = slab.element_size()
+    if out is None:
+        out = torch.empty(shape, dtype=slab.dtype, device=slab.device)
+    else:
+        try:
+            _expect("pool_labels: out", out, slab.dtype, shape)
+        except HipError as e:
+            raise ValueError(str(e)) from None
+        if out.device != slab.device or not out.is_contiguous():
+            raise ValueError(f"pool_labels: out must be contiguous and on {slab.device}")
+        a0, b0 = slab.data_ptr(), out.data_ptr()
+        if slab.numel() and a0 < b0 + out.numel() * item and b0 < a0 + slab.numel() * item:
+            raise ValueError("pool_labels: out overlaps the slab")
+    require_gpu()
+    if slab.numel():
+        D, H, W = (int(s) for s in slab.shape)
+        with torch.cuda.device(slab.device):
+            call('emp_label_pool_mode', _ptr(slab), item, D, H, W, f[0], f[1], f[2], _ptr(out), _current_stream(),
+                 alg_bytes=(slab.numel() + out.numel()) * item)
+    return out
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

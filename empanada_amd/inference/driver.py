@@ -21,6 +21,7 @@ import torch
 from .. import _hip
 from ..data import DeviceVolume
 from ..zarr_utils import ZarrV2Group
+from . import pyramid as pyr
 from . import sharded, windowed
 from .engines import logits_to_prob
 
@@ -99,21 +100,57 @@ def forward_heads(model, margs, dv, axis, lo, hi, per, bufs, at=0):
                     {k: v[at + s - lo:at + e - lo] for k, v in bufs.items()})
 
 
-def open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor=None):
+def dataset_names(labels, class_names):
+    return {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}
+
+
+def open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor=None, levels=()):
     """{class: the '<class name>_pred' array of `out`, or None without one}: uint32 for thing classes, uint8 for stuff,
     chunks (1, Y, X) (pdl_inference3d.py:225-233); rank 0 creates them before any rank opens one.  compressor='zlib':
-    created with {"id": "zlib", "level": 1} (the reference's datasets are compressed too, :228-233)"""
+    created with {"id": "zlib", "level": 1} (the reference's datasets are compressed too, :228-233).  levels: the plan of
+    a pyramid (pyramid.plan) -- rank 0 also creates '<class name>_pred_s<l>' for level l = 1 .. with the level's shape
+    and the dtype, chunking and compressor of level 0, before the same barrier; open_level_datasets opens them"""
     if out is None:
         return {c: None for c in labels}
-    names = {c: f"{(class_names or {}).get(c, c)}_pred" for c in labels}
+    names = dataset_names(labels, class_names)
     extra = {} if compressor is None else {'compressor': {'id': 'zlib', 'level': 1}}
     if rank == 0:
         for c in labels:
-            out.create_dataset(names[c], shape=shape3d, dtype=np.uint32 if c in thing_list else np.uint8,
-                               overwrite=True, chunks=(1, None, None), **extra)
+            for l, shape in enumerate([shape3d] + [lv['shape'] for lv in levels]):
+                out.create_dataset(names[c] + (f"_s{l}" if l else ""), shape=shape,
+                                   dtype=np.uint32 if c in thing_list else np.uint8, overwrite=True,
+                                   chunks=(1, None, None), **extra)
     if world > 1:
         torch.distributed.barrier(group=group)
     return {c: out[names[c]] for c in labels}
+
+
+def open_level_datasets(out, labels, class_names, levels):
+    """{class: [the '<class name>_pred_s<l>' array of level l = 1 .., or None without `out`]}, after open_datasets"""
+    names = dataset_names(labels, class_names)
+    return {c: [None if out is None else out[f"{names[c]}_s{l}"] for l in range(1, len(levels) + 1)] for c in labels}
+
+
+def pyramid_levels(pyramid, shape3d, world):
+    """infer_volume's `pyramid` argument -> the plan (pyramid.plan) of every rank's z-slab, before any GPU work: a
+    ValueError for a bad value or for a slab that a level's cells would straddle, on every rank alike"""
+    return pyr.check_ranks(shape3d, pyr.normalize(pyramid), sharded.shard_bounds(int(shape3d[0]), world))
+
+
+def write_multiscales(out, labels, class_names, levels):
+    """one OME-NGFF `multiscales` entry per class into the attributes of `out` (rank 0, after its levels are written):
+    entries of other names are kept, one of the same name is replaced; an `out` without attributes gets none"""
+    names = dataset_names(labels, class_names)
+    cum = [(1, 1, 1)] + [lv['factor'] for lv in levels]
+    new = [pyr.multiscales(names[c], [names[c]] + [f"{names[c]}_s{l}" for l in range(1, len(cum))], cum) for c in labels]
+    if not isinstance(out, ZarrV2Group) and not hasattr(out, 'attrs'):
+        return
+    mine = {e['name'] for e in new}
+    kept = [e for e in out.attrs.get('multiscales', []) if not (isinstance(e, dict) and e.get('name') in mine)]
+    if isinstance(out, ZarrV2Group):
+        out.update_attrs({'multiscales': kept + new})
+    else:
+        out.attrs['multiscales'] = kept + new
 
 
 def host_slab(vol, thing):
@@ -121,12 +158,14 @@ def host_slab(vol, thing):
     return vol.view(torch.int32).cpu().numpy().view(np.uint32) if thing else vol.cpu().numpy()
 
 
-def result(vols, z_range, counts, datasets, windows=None, head_bytes=0, pipeline=None, compressed=None):
+def result(vols, z_range, counts, datasets, windows=None, head_bytes=0, pipeline=None, compressed=None, pyramid=None):
     """infer_volume's result; windows ({axis: steps}): a windowed call, which also reports the head buffers it held;
-    compressed ({class: bytes}): a call with compressor='zlib'"""
+    compressed ({class: bytes}): a call with compressor='zlib'; pyramid: a call with pyramid=, the keys it adds"""
     res = {'volumes': vols, 'z_range': z_range, 'instances': counts, 'datasets': datasets}
     if compressed is not None:
         res['compressed_bytes'] = compressed
+    if pyramid is not None:
+        res.update(pyramid)
     if windows is not None:
         res.update(windows=windows, head_bytes=int(head_bytes))
     if pipeline is not None:
@@ -224,7 +263,7 @@ def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, win
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
-                 window_slices=None, mem_budget=None, ground_truth=None, compressor=None):
+                 window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -255,11 +294,24 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     rank's slab of every class is made zlib streams on the device (ZarrV2Array.write_slab_device), so only compressed
     bytes cross to the host and reach the disk, and no CPU compresses; needs out= to be a ZarrV2Group.  The result
     gains 'compressed_bytes': {class: bytes this rank wrote}.  The volumes and what the datasets read back are the same.
+    pyramid: None = level 0 only; an integer L (1..8) = L more levels, each the level below pooled by (2, 2, 2); a
+    sequence of factor triples of 1s and 2s = one level per triple ((1, 2, 2) for thick serial sections).  A level's
+    voxel is the most frequent label of its cell, the largest among equally frequent ones (inference/pyramid.py,
+    _hip.pool_labels), computed on the device from the resident slab: uint32 for thing classes, uint8 for stuff.  With
+    out=, level l of a class is the dataset '<class name>_pred_s<l>' with the dtype, chunking and compressor of level
+    0, and the group's attributes gain one OME-NGFF 0.4 `multiscales` entry per class.  Every rank pools its own
+    z-slab, so a slab must be aligned to every level's cumulative z-factor (ValueError otherwise, on every rank,
+    before any work: fewer ranks, fewer levels or (1, 2, 2) levels).  The result gains 'pyramid': {class: [the rank's
+    slab of level 1, ...]}, 'pyramid_z_ranges': [(z0, z1) of the rank per level], 'pyramid_datasets': {class: [array or
+    None, ...]} and, with a compressor, 'pyramid_compressed_bytes': {class: [bytes per level]}.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
     window_slices = _check_windows(window_slices, mem_budget, pipeline, world)
     _check_compressor(compressor, out)
+    levels = None
+    if pyramid is not None:
+        levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
     labels = list(labels)
     thing_list = list(engine.thing_list)
     div = engine.label_divisor
@@ -309,7 +361,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
                            track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices,
-                           compressor=compressor)
+                           compressor=compressor, levels=levels)
         return _scored(res, ground_truth, thing_list, group)
     planes, base = {}, 0
     windows = {'windows': {}, 'head_bytes': 0}
@@ -327,7 +379,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         base += planes[axis].n_inst
         del pan
     vols, (z0, z1), counts = finish(planes)
-    datasets = open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor)
+    datasets = open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor, levels or ())
     compressed = None if compressor is None else {}
     if out is not None:
         for c in labels:
@@ -335,5 +387,20 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                 datasets[c].write_slab(z0, host_slab(vols[c], c in thing_list))
             else:
                 compressed[c] = datasets[c].write_slab_device(z0, vols[c].contiguous())[1]
-    return _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed,
+    extra = None
+    if levels is not None:
+        extra = {'pyramid': {c: pyr.build(vols[c].contiguous(), [lv['pool'] for lv in levels]) for c in labels},
+                 'pyramid_z_ranges': [lv['z_range'] for lv in levels],
+                 'pyramid_datasets': open_level_datasets(out, labels, class_names, levels)}
+        if compressor is not None:
+            extra['pyramid_compressed_bytes'] = {c: [] for c in labels}
+        for c in labels if out is not None else ():
+            for lv, slab, ds in zip(levels, extra['pyramid'][c], extra['pyramid_datasets'][c]):
+                if compressor is None:
+                    ds.write_slab(lv['z_range'][0], host_slab(slab, c in thing_list))
+                else:
+                    extra['pyramid_compressed_bytes'][c].append(ds.write_slab_device(lv['z_range'][0], slab)[1])
+        if out is not None and rank == 0:
+            write_multiscales(out, labels, class_names, levels)
+    return _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed, pyramid=extra,
                           **(windows if window_slices is not None else {})), ground_truth, thing_list, group)

@@ -16,7 +16,9 @@ What it changes against the plain call (driver._plane_heads + the serial plane l
     'auto' falls back to one set and serial planes when two planes' heads do not fit;
   * writing: the labelled slab goes to the zarr array through SlabWriter (pinned buffer, asynchronous copy, chunk files
     written by a pool while the next class is copied); with infer_volume(..., compressor='zlib') the slab is made zlib
-    streams on the post stream first (ZarrV2Array.write_slab_device) and only those bytes are copied and written.
+    streams on the post stream first (ZarrV2Array.write_slab_device) and only those bytes are copied and written; with
+    infer_volume(..., pyramid=) every class's level slabs are pooled on the post stream (inference/pyramid.py) and go
+    the same way, each level through a writer and a pinned buffer of its own, keyed (class, level).
 With infer_volume(..., window_slices=) the planes stream through windows of slices (inference/windowed.py) and the two
 sets of buffers alternate per step of a plane instead of per plane (_run_windowed).
 What a plane is -- slices per model call, the model's arguments, head shapes, the loop that writes every batch's heads,
@@ -30,7 +32,7 @@ import numpy as np
 import torch
 
 from ..zarr_utils import SlabWriter, ZarrV2Array
-from . import driver, sharded, windowed
+from . import driver, pyramid, sharded, windowed
 
 __all__ = ['VolumePipeline']
 
@@ -85,7 +87,7 @@ class VolumePipeline:
         self._store = [None, None]                    # flat fp32 storage of the two sets of plane buffers
         self._writers = {}
         self._zpool = None                            # compressor='zlib': the writer threads ...
-        self._zbufs = {}                              # ... and one pinned buffer of compressed bytes per class
+        self._zbufs = {}                              # ... and one pinned buffer of compressed bytes per class (and level)
 
     # ------------------------------------------------------------------------------------------ checks, before GPU work
     def _param(self):
@@ -234,7 +236,7 @@ class VolumePipeline:
 
     # ------------------------------------------------------------------------------------------ the volume
     def run(self, dv, *, axes, labels, thing_list, params, steps, group, track, finish, class_names, out,
-            window_slices=None, compressor=None):
+            window_slices=None, compressor=None, levels=None):
         """Called by infer_volume after its own argument checks.  track(pan, axis, base) and finish(planes) are the
         driver's own plane and volume steps, so both paths share them.  The loops over planes (_run_planes) or over the
         steps of every plane (_run_windowed, window_slices=) plan and allocate first and hand back their `walk`; all
@@ -267,18 +269,21 @@ class VolumePipeline:
         with self._deferring(), torch.cuda.stream(post):
             planes, windows, hist_bytes = walk(model, fwd, post)
             vols, (z0, z1), counts = finish(planes)
-            datasets, compressed = self._write(out, vols, z0, labels, thing_list, class_names, dv.shape, rank, world,
-                                               group, post, compressor)
+            slabs = None                                  # pyramid=: every class's level slabs, pooled on the post stream
+            if levels is not None:
+                slabs = {c: pyramid.build(vols[c].contiguous(), [lv['pool'] for lv in levels]) for c in labels}
+            datasets, compressed, extra = self._write(out, vols, z0, labels, thing_list, class_names, dv.shape, rank,
+                                                      world, group, post, compressor, levels, slabs)
         cur.wait_stream(post)
         cur.wait_stream(fwd)
-        for v in vols.values():
+        for v in list(vols.values()) + [s for lst in (slabs or {}).values() for s in lst]:
             v.record_stream(cur)                          # allocated on the post stream, handed to the caller's
         head_bytes = self._held() + hist_bytes
         pipe = {'tuned': self.tuned_counts(), 'graph': bool(graph), 'overlap': bool(overlap), 'head_bytes': int(head_bytes)}
         if windows is not None:
             pipe['windows'] = windows
         pipe['captures'] = (self._graphed.captures - captured) if graph else 0
-        return driver.result(vols, (z0, z1), counts, datasets, windows, head_bytes, pipe, compressed)
+        return driver.result(vols, (z0, z1), counts, datasets, windows, head_bytes, pipe, compressed, extra)
 
     def _run_planes(self, dv, plan, shapes, margs, params, group, track, out_bytes):
         """Whole planes: the two sets of head buffers alternate per plane, the forward of plane i + 2 is queued as soon as
@@ -396,7 +401,8 @@ class VolumePipeline:
 
     # ------------------------------------------------------------------------------------------ writing
     def _writer(self, c, array, z0, shape, dtype):
-        """one SlabWriter (pool + pinned buffer) per class and slab shape, kept across volumes: pinning is slow"""
+        """one SlabWriter (pool + pinned buffer) per key c -- a class, or (class, level) for a pyramid's levels -- and slab
+        shape, kept across volumes: pinning is slow"""
         key = (c, tuple(shape), dtype)
         w = self._writers.get(key)
         if w is None:
@@ -407,46 +413,76 @@ class VolumePipeline:
         return w
 
     def _pinned(self, c, nbytes):
-        """class c's pinned buffer for compressed bytes: sized by what a slab actually took, and only ever grown"""
+        """the pinned buffer for compressed bytes of key c (a class, or (class, level)): sized by what a slab actually
+        took, and only ever grown"""
         buf = self._zbufs.get(c)
         if buf is None or buf.numel() < nbytes:
             buf = self._zbufs[c] = torch.empty((max(nbytes, 1),), dtype=torch.uint8).pin_memory()
         return buf
 
-    def _write_compressed(self, datasets, vols, z0, labels):
-        """compressor='zlib': every class's slab is encoded on the post stream (the current one), its compressed bytes are
-        copied into the class's pinned buffer, and the chunk files are written by the pool while the next class is
-        encoded.  Returns {class: bytes written}"""
+    @staticmethod
+    def _jobs(datasets, vols, z0, labels, levels, slabs, level_sets):
+        """what a volume writes, as (key, class, array, first slice, slab): level 0 of every class under the class itself
+        as key, level l of a pyramid under (class, l) -- the keys of the writers and of the pinned buffers, so that the
+        levels of one class, whose slab shapes differ, do not evict one another"""
+        jobs = [(c, c, datasets[c], z0, vols[c]) for c in labels]
+        for c in labels if levels is not None else ():
+            for l, (lv, slab, ds) in enumerate(zip(levels, slabs[c], level_sets[c]), start=1):
+                jobs.append(((c, l), c, ds, lv['z_range'][0], slab))
+        return jobs
+
+    def _write_compressed(self, jobs):
+        """compressor='zlib': every slab is encoded on the post stream (the current one), its compressed bytes are copied
+        into its key's pinned buffer, and the chunk files are written by the pool while the next slab is encoded.
+        Returns {key: bytes written}"""
         if self._zpool is None:
             from concurrent.futures import ThreadPoolExecutor
             self._zpool = ThreadPoolExecutor(max_workers=4)
         pending, compressed = [], {}
-        for c in labels:
-            futures, compressed[c] = datasets[c].write_slab_device(z0, vols[c].contiguous(), self._zpool,
-                                                                   host=lambda n, c=c: self._pinned(c, n))
+        for key, _, arr, zs, slab in jobs:
+            futures, compressed[key] = arr.write_slab_device(zs, slab.contiguous(), self._zpool,
+                                                             host=lambda n, key=key: self._pinned(key, n))
             pending += futures
         for f in pending:
             f.result()
         return compressed
 
-    def _write(self, out, vols, z0, labels, thing_list, class_names, shape3d, rank, world, group, post, compressor=None):
-        datasets = driver.open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor)
+    def _write(self, out, vols, z0, labels, thing_list, class_names, shape3d, rank, world, group, post, compressor=None,
+               levels=None, slabs=None):
+        """the datasets, {class: compressed bytes} or None, and the result keys of a pyramid (levels: the rank's plan,
+        slabs: {class: its level slabs}) or None"""
+        datasets = driver.open_datasets(out, labels, thing_list, class_names, shape3d, rank, world, group, compressor,
+                                        levels or ())
+        extra = level_sets = None
+        if levels is not None:
+            level_sets = driver.open_level_datasets(out, labels, class_names, levels)
+            extra = {'pyramid': slabs, 'pyramid_z_ranges': [lv['z_range'] for lv in levels],
+                     'pyramid_datasets': level_sets}
+        jobs = self._jobs(datasets, vols, z0, labels, levels, slabs, level_sets) if out is not None else []
+        compressed = None
         if compressor is not None:
-            return datasets, self._write_compressed(datasets, vols, z0, labels)
-        used = []
-        for c in labels if out is not None else ():
-            arr, thing = datasets[c], c in thing_list
-            if isinstance(arr, ZarrV2Array):
-                w = self._writer(c, arr, z0, vols[c].shape, torch.int32 if thing else torch.uint8)
-                w.next_buffer().copy_(vols[c].view(torch.int32) if thing else vols[c], non_blocking=True)
-                post.synchronize()                        # the post stream only
-                w.submit()                                # chunk files by the pool, while the next class is copied
-                used.append(w)
-            else:
-                arr.write_slab(z0, driver.host_slab(vols[c], thing))
-        for w in used:
-            w.drain()
-        return datasets, None
+            nbytes = self._write_compressed(jobs)
+            compressed = {c: nbytes[c] for c in labels}
+            if levels is not None:
+                extra['pyramid_compressed_bytes'] = {c: [nbytes[(c, l)] for l in range(1, len(levels) + 1)]
+                                                     for c in labels}
+        else:
+            used = []
+            for key, c, arr, zs, slab in jobs:
+                thing = c in thing_list
+                if isinstance(arr, ZarrV2Array):
+                    w = self._writer(key, arr, zs, slab.shape, torch.int32 if thing else torch.uint8)
+                    w.next_buffer().copy_(slab.view(torch.int32) if thing else slab, non_blocking=True)
+                    post.synchronize()                    # the post stream only
+                    w.submit()                            # chunk files by the pool, while the next slab is copied
+                    used.append(w)
+                else:
+                    arr.write_slab(zs, driver.host_slab(slab, thing))
+            for w in used:
+                w.drain()
+        if levels is not None and out is not None and rank == 0:
+            driver.write_multiscales(out, labels, class_names, levels)
+        return datasets, compressed, extra
 
     def close(self):
         for w in self._writers.values():

@@ -380,6 +380,22 @@ class ZarrV2Group:
             json.dump(meta, fh, indent=4)
         return ZarrV2Array(path, meta)
 
+    @property
+    def attrs(self):
+        """the group's user attributes: the parsed `.zattrs` document, {} without one"""
+        p = os.path.join(self.path, '.zattrs')
+        if not os.path.exists(p):
+            return {}
+        with open(p) as fh:
+            return json.load(fh)
+
+    def update_attrs(self, mapping):
+        """merge `mapping` into the group's attributes (a key that exists is replaced) and rewrite `.zattrs`"""
+        attrs = self.attrs
+        attrs.update(mapping)
+        with open(os.path.join(self.path, '.zattrs'), 'w') as fh:
+            json.dump(attrs, fh, indent=4)
+
     def __getitem__(self, name):
         return ZarrV2Array(os.path.join(self.path, name))
 

@@ -658,6 +658,22 @@ int emp_deflate_count(const void *src, int item, int64_t n_chunks, int64_t chunk
 int emp_deflate_encode(const void *src, int item, int64_t n_chunks, int64_t chunk_bytes, void *work,
                        int64_t work_bytes, int64_t total, uint8_t *out, int64_t out_bytes, void *stream);
 
+/* ---- Z2: one level of a multiscale label pyramid: mode pooling on the device -------------------------------------
+ * no counterpart in the reference: its label volumes are written at full resolution only (scripts/pdl_inference3d.py:
+ * 225-233) and viewers (napari, neuroglancer, every OME-NGFF reader) down-sample them on the CPU after the fact.
+ * src is a contiguous (D, H, W) array of item-byte unsigned little-endian integers, item = 1 (uint8) or 4 (uint32);
+ * fz, fy, fx are each 1 or 2, at least one of them 2; dst is a contiguous (ceil(D / fz), ceil(H / fy), ceil(W / fx))
+ * array of the same item size that does not overlap src.
+ * dst[z, y, x] = the value that occurs most often among the src voxels of the cell [fz z, fz z + fz) x [fy y, fy y +
+ * fy) x [fx x, fx x + fx) clipped to the volume (at odd sizes the last cells hold 4, 2 or 1 voxels); among values that
+ * occur equally often the LARGEST wins, compared as unsigned numbers.  So background 0 never wins a tie, a sheet one
+ * voxel thick survives a 4 : 4 split, and the result does not depend on any visiting order.
+ * One streaming pass: reads fz fy fx elements and writes one per output voxel, 16-byte loads and stores where the
+ * rows of src (W * item) and of dst start on 16-byte addresses, element-wise ones with the same results otherwise;
+ * all index arithmetic is 64-bit.  No workspace, no allocation, no synchronisation; an empty volume is a no-op.  */
+int emp_label_pool_mode(const void *src, int item, int64_t D, int64_t H, int64_t W, int fz, int fy, int fx, void *dst,
+                        void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38

@@ -9,10 +9,14 @@ two device synchronisations.  One JSON line.
 
     python tools/bench_infer_volume.py --size 512 [--model pdl_r50|mitonet_pr] [--axes xy,xz,yz] [--paths plain,pipeline]
                                        [--repeats 3] [--warmup 1] [--no-tune] [--no-graph] [--overlap auto|on|off]
-                                       [--window-slices W|auto]
+                                       [--window-slices W|auto] [--pyramid L] [--compressor zlib]
 
 --window-slices streams every plane through windows of W slices (inference/windowed.py) on the paths named; the row then
 holds the steps per plane and the bytes of head buffers held (profiles/windowed_planes.md).
+
+--pyramid L adds L (2, 2, 2) levels of a multiscale pyramid to every call (inference/pyramid.py; the levels are pooled on
+the device and written beside level 0), --compressor zlib writes every level as zlib streams made on the device; the
+same command without them is the comparison (profiles/label_pyramid.md).
 
 --split also times the forwards of the three planes alone (heads written in place, no post-processing) on the pipeline's
 own code, so that a volume whose random heads make the post-processing dominate can be read.
@@ -90,6 +94,8 @@ def main():
     ap.add_argument('--overlap', default='auto', choices=['auto', 'on', 'off'])
     ap.add_argument('--split', action='store_true', help='also time the forwards alone')
     ap.add_argument('--window-slices', default=None, help="slices per window, or 'auto'; default: whole planes")
+    ap.add_argument('--pyramid', type=int, default=None, help='levels of a (2, 2, 2) label pyramid to add')
+    ap.add_argument('--compressor', default=None, choices=['zlib'])
     ap.add_argument('--out', default=None, help='write the JSON line to this file as well')
     args = ap.parse_args()
     _hip.require_gpu()
@@ -107,8 +113,12 @@ def main():
     kw = dict(norms=NORMS, labels=[1], axes=axes, class_names={1: 'mito'}, out=ZarrV2Group(store))
     if args.window_slices is not None:
         kw['window_slices'] = 'auto' if args.window_slices == 'auto' else int(args.window_slices)
+    if args.pyramid is not None:
+        kw['pyramid'] = args.pyramid
+    if args.compressor is not None:
+        kw['compressor'] = args.compressor
     row = {'size': args.size, 'model': args.model, 'axes': list(axes), 'batch_pixels': args.batch_pixels,
-           'window_slices': kw.get('window_slices'),
+           'window_slices': kw.get('window_slices'), 'pyramid': args.pyramid, 'compressor': args.compressor,
            'device': torch.cuda.get_device_name(0), 'repeats': args.repeats, 'warmup': args.warmup}
     fns, pipe, last = {}, None, {}
     try:
