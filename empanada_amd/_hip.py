@@ -117,6 +117,10 @@ SIGNATURES = {
     'emp_deflate_count': (_I, [_P, _I, _L, _L, _P, _L, _P, _P]),
     'emp_deflate_encode': (_I, [_P, _I, _L, _L, _P, _L, _L, _P, _L, _P]),
     'emp_label_pool_mode': (_I, [_P, _I, _L, _L, _L, _I, _I, _I, _P, _P]),
+    'emp_label_measure_count_work_bytes': (_L, [_L]),
+    'emp_label_measure_count': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _P]),
+    'emp_label_measure_work_bytes': (_L, [_L]),
+    'emp_label_measure': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -695,6 +699,98 @@ def pool_labels(slab, factors=(2, 2, 2), out=None):
             call('emp_label_pool_mode', _ptr(slab), item, D, H, W, f[0], f[1], f[2], _ptr(out), _current_stream(),
                  alg_bytes=(slab.numel() + out.numel()) * item)
     return out
+
+
+MEASURE_MAX_VOXELS = 2 ** 31 - 1     # voxels per emp_label_measure call: one run per voxel must fit the int32 scan
+MEASURE_COLUMNS = 14
+
+
+def _measure_operand(what, t, dtype=None, shape=None, device=None):
+    try:
+        _expect(f"measure_labels: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if not t.is_contiguous():
+        raise ValueError(f"measure_labels: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"measure_labels: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, info=None):
+    """Per-object measurements of a label slab (emp_label_measure; the definition is in include/emp_hip.h, E2): an
+    (n, 14) int64 table on the slab's device, one row per distinct non-zero label, ascending by label -- label, voxels,
+    z0 y0 x0, z1 y1 x1 (largest index + 1), sum_z sum_y sum_x, faces_z faces_y faces_x (measurements.COLUMNS).  slab:
+    (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they are).  below / above: (H, W)
+    tensors of the slab's dtype and device that stand for the slices at z = -1 and z = D, None = background; z_base is
+    added to every z index.  A slab of more than block_voxels voxels (None: MEASURE_MAX_VOXELS, the kernel's limit) is
+    cut into z-blocks of whole slices, each measured with its true neighbour slices -- views of the slab, or below /
+    above at its ends -- and its own z_base, and the block tables are merged on the device
+    (measurements.merge_tables); a single slice above the limit is a ValueError.  An empty or all-zero slab gives a
+    (0, 14) table.  Two host syncs per block (run count, label count).  info: a dict that receives 'blocks' (kernel
+    calls made), 'runs' (runs they sorted) and 'work_bytes' (largest workspace of one call)."""
+    import numbers
+    slab = _measure_operand("slab", slab)
+    if slab.dim() != 3:
+        raise ValueError(f"measure_labels: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if below is not None:
+        below = _measure_operand("below", below, slab.dtype, (H, W), dev)
+    if above is not None:
+        above = _measure_operand("above", above, slab.dtype, (H, W), dev)
+    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
+        raise ValueError(f"measure_labels: z_base must be a non-negative integer, got {z_base!r}")
+    if block_voxels is None:
+        block_voxels = MEASURE_MAX_VOXELS
+    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
+          or not 1 <= block_voxels <= MEASURE_MAX_VOXELS):
+        raise ValueError(f"measure_labels: block_voxels must lie in 1 .. {MEASURE_MAX_VOXELS}, got {block_voxels!r}")
+    stats = {} if info is None else info
+    stats.update(blocks=0, runs=0, work_bytes=0)
+    empty = torch.zeros((0, MEASURE_COLUMNS), dtype=torch.int64, device=dev)
+    if slab.numel() == 0:
+        return empty
+    if H * W > block_voxels:
+        raise ValueError(f"measure_labels: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    require_gpu()
+    item = slab.element_size()
+    per = max(1, int(block_voxels) // (H * W))
+    tables = []
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            part = slab[z0:z1]
+            lo = below if z0 == 0 else slab[z0 - 1]
+            hi = above if z1 == D else slab[z1]
+            d = z1 - z0
+            rows = d * H
+            wb = query('emp_label_measure_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_measure_count', _ptr(part), item, d, H, W, _ptr(work), wb, _ptr(offs), _current_stream(),
+                 alg_bytes=rows * W * item)
+            n_runs = int(offs[-1].item())
+            stats['blocks'] += 1
+            stats['runs'] += n_runs
+            if n_runs == 0:
+                continue
+            wb = query('emp_label_measure_work_bytes', n_runs)
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            table = torch.empty((n_runs, MEASURE_COLUMNS), dtype=torch.int64, device=dev)
+            n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_measure', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), int(z_base) + z0, _ptr(offs), n_runs,
+                 _ptr(work), wb, _ptr(table), _ptr(n_out), _current_stream(), alg_bytes=rows * W * item)
+            # the capacity is one row per run: keep the table only
+            tables.append(table[:int(n_out.item())].clone())
+    if not tables:
+        return empty
+    if len(tables) == 1:
+        return tables[0]
+    from .measurements import merge_tables
+    return merge_tables(tables)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -237,6 +237,92 @@ def _scored(res, ground_truth, thing_list, group):
     return res
 
 
+def _check_measure(measure):
+    """infer_volume's `measure` argument -> None or the voxel spacing (sz, sy, sx), before any GPU work"""
+    if measure is None:
+        return None
+    if measure is True:
+        return (1.0, 1.0, 1.0)
+    bad = ValueError(f"measure must be None, True or a voxel spacing (sz, sy, sx) of three positive numbers, got {measure!r}")
+    if isinstance(measure, (bool, np.bool_, str, bytes)):
+        raise bad
+    try:
+        values = list(measure)
+    except TypeError:
+        raise bad from None
+    import numbers
+    if len(values) != 3 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) for v in values):
+        raise bad
+    spacing = tuple(float(v) for v in values)
+    if not all(np.isfinite(v) and v > 0 for v in spacing):
+        raise bad
+    return spacing
+
+
+def object_dataset_names(labels, class_names):
+    return {c: f"{(class_names or {}).get(c, c)}_objects" for c in labels}
+
+
+def _neighbour_slices(slab, group):
+    """(below, above) of a rank's slab: the last slice of the nearest rank below and the first slice of the nearest
+    rank above that hold any slice, None at the volume's ends -- one gather of every rank's two end slices"""
+    rank, world = sharded._world(group)
+    if world == 1:
+        return None, None
+    bits = slab.view(torch.int32) if slab.dtype == torch.uint32 else slab      # torch copies few uint32 tensors
+    ends = torch.stack([bits[0], bits[-1]]) if bits.shape[0] else bits[:0]
+    parts = [p.view(slab.dtype) if p.dtype != slab.dtype else p for p in sharded._gather_var(ends.contiguous(), group)]
+    below = next((parts[r][1] for r in range(rank - 1, -1, -1) if parts[r].shape[0]), None)
+    above = next((parts[r][0] for r in range(rank + 1, world) if parts[r].shape[0]), None)
+    return (None if below is None else below.contiguous()), (None if above is None else above.contiguous())
+
+
+def _measured(res, spacing, labels, class_names, out, group):
+    """the result with 'objects': every rank measures its slab of every class (_hip.measure_labels, z_base = z0) with the
+    neighbouring ranks' end slices standing for what lies outside it, the tables are merged over the ranks, and rank 0
+    writes one '<class name>_objects' dataset per class"""
+    if spacing is None:
+        return res
+    from ..measurements import COLUMNS, gather_tables
+    rank, world = sharded._world(group)
+    z0 = int(res['z_range'][0])
+    objects = {}
+    for c in labels:
+        slab = res['volumes'][c].contiguous()
+        below, above = _neighbour_slices(slab, group)
+        objects[c] = gather_tables(_hip.measure_labels(slab, below=below, above=above, z_base=z0), group).cpu().numpy()
+    res['objects'] = objects
+    res['object_spacing'] = spacing
+    if out is None:
+        return res
+    names = object_dataset_names(labels, class_names)
+    left_out = set()
+    if rank == 0:
+        for c in labels:
+            table = objects[c]
+            try:
+                ds = out.create_dataset(names[c], shape=table.shape, dtype=np.int64, overwrite=True,
+                                        chunks=(max(table.shape[0], 1), table.shape[1]))
+                if table.shape[0]:
+                    ds[...] = table
+            except Exception:
+                if table.shape[0]:
+                    raise
+                left_out.add(c)                      # a store that cannot hold a zero-row array
+        attrs = {'objects': {'columns': list(COLUMNS), 'spacing': list(spacing)}}
+        if isinstance(out, ZarrV2Group):
+            out.update_attrs(attrs)
+        elif hasattr(out, 'attrs'):
+            out.attrs.update(attrs)
+    if world > 1:
+        flag = [sorted(left_out, key=str)]
+        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
+        left_out = set(flag[0])
+    res['object_datasets'] = {c: None if c in left_out else out[names[c]] for c in labels}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -263,7 +349,8 @@ def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, win
 def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merge_iou_thr=0.25, merge_ioa_thr=0.25,
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
-                 window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None):
+                 window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
+                 measure=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -304,11 +391,22 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     before any work: fewer ranks, fewer levels or (1, 2, 2) levels).  The result gains 'pyramid': {class: [the rank's
     slab of level 1, ...]}, 'pyramid_z_ranges': [(z0, z1) of the rank per level], 'pyramid_datasets': {class: [array or
     None, ...]} and, with a compressor, 'pyramid_compressed_bytes': {class: [bytes per level]}.
+    measure: None = no table, nothing else changes; True, or a voxel spacing (sz, sy, sx) of three positive numbers = once
+    the volumes exist every rank measures its z-slab of every class on the device (_hip.measure_labels; the table is
+    defined in include/emp_hip.h, E2) with the end slices of the ranks next to it standing for what lies outside the
+    slab, and the tables are merged over the ranks.  The result gains 'objects': {class: (n, 14) int64 numpy table of
+    the WHOLE volume, the same on every rank, one row per label ascending: measurements.COLUMNS} -- at most one row
+    (label 1) for a stuff class -- and 'object_spacing': the spacing (True: (1, 1, 1)), which measurements.derive
+    turns into volumes, centroids, boxes and surface areas.  With out=, rank 0 writes one dataset
+    '<class name>_objects' per class (int64, (n, 14), one raw chunk), the group's attributes gain 'objects':
+    {'columns', 'spacing'} beside what they hold, and the result gains 'object_datasets': {class: array, or None where
+    the store cannot hold the zero-row table of a class without objects}.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
     window_slices = _check_windows(window_slices, mem_budget, pipeline, world)
     _check_compressor(compressor, out)
+    spacing = _check_measure(measure)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -362,7 +460,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
                            track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices,
                            compressor=compressor, levels=levels)
-        return _scored(res, ground_truth, thing_list, group)
+        return _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
     planes, base = {}, 0
     windows = {'windows': {}, 'head_bytes': 0}
     for axis in axes:
@@ -402,5 +500,6 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                     extra['pyramid_compressed_bytes'][c].append(ds.write_slab_device(lv['z_range'][0], slab)[1])
         if out is not None and rank == 0:
             write_multiscales(out, labels, class_names, levels)
-    return _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed, pyramid=extra,
-                          **(windows if window_slices is not None else {})), ground_truth, thing_list, group)
+    res = _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed, pyramid=extra,
+                         **(windows if window_slices is not None else {})), ground_truth, thing_list, group)
+    return _measured(res, spacing, labels, class_names, out, group)

@@ -674,6 +674,45 @@ int emp_deflate_encode(const void *src, int item, int64_t n_chunks, int64_t chun
 int emp_label_pool_mode(const void *src, int item, int64_t D, int64_t H, int64_t W, int fz, int fy, int fx, void *dst,
                         void *stream);
 
+/* ---- E2: per-object measurements of a label volume (voxels, box, index sums, exposed faces) ------------------------
+ * no counterpart in the reference: its trackers carry boxes and runs per plane, before the consensus
+ * (empanada/inference/tracker.py:61-123); the morphology of the final objects is left to CPU code run afterwards.
+ * lab is a contiguous (D, H, W) array of item-byte unsigned little-endian integers, item = 1 (uint8) or 4 (uint32; the
+ * bits of an int32 are taken as they are), 0 = background.  The table has one row of 14 int64 per distinct non-zero
+ * label, ascending by label as an unsigned number:
+ *     0        label
+ *     1        voxels
+ *     2..4     z0, y0, x0   smallest index per axis, z counted as z_base + local z
+ *     5..7     z1, y1, x1   largest index + 1
+ *     8..10    sum_z, sum_y, sum_x   sums of the voxel indices (z including z_base)
+ *     11..13   faces_z, faces_y, faces_x   exposed voxel faces normal to each axis
+ * A face of a voxel is exposed when the voxel on its other side carries a different value; background counts as
+ * different and a position outside the array reads as 0.  Along z the block has two optional neighbour slices, `below`
+ * (z = -1) and `above` (z = D), each a contiguous (H, W) array of the same item size, which stand in for what lies
+ * outside the block; a null pointer means 0.  Columns 1 and 8..13 are sums and 2..7 minima / maxima of integers, so the
+ * table of a volume equals the merge (sum, min, max per label) of the tables of any z-partition of it whose blocks
+ * were given their true neighbour slices, and no visiting order shows in the result.  The face count is the "crack"
+ * area: exact and additive, but it overestimates a smooth surface (1.5 x for a sphere).
+ * Step 1  emp_label_measure_count: row_offsets[0..R] (R + 1 int32, R = D * H) = exclusive prefix sum of the number of
+ *         maximal runs of one non-zero label per row; row_offsets[R] is the run total n_runs, which sizes step 2
+ *         exactly.  work: emp_label_measure_count_work_bytes(R) bytes.
+ * Step 2  emp_label_measure: runs -> (label, row, x start, length, y exposure, z exposure) -> sort by label -> one row
+ *         per label.  out_table (n_runs, 14) int64 receives n_out (device int32[1]) rows; the labels must not have
+ *         changed since step 1 (a run past n_runs is dropped, never written).  work: emp_label_measure_work_bytes(
+ *         n_runs) bytes.
+ * A call covers at most 2^31 - 1 voxels (D * H * W; one run per voxel is the worst case and the scan is int32): a
+ * larger block is refused with EMP_EINVAL, never truncated -- callers cut the slab into z-blocks, hand each its
+ * neighbour slices and merge the tables (_hip.measure_labels does).  Step 1 reads every voxel once; step 2 reads every
+ * voxel once and, for the lanes that hold a non-zero voxel, the same positions of rows y +- 1 and z +- 1; all else is
+ * O(n_runs).                                                                                                        */
+int64_t emp_label_measure_count_work_bytes(int64_t R);
+int emp_label_measure_count(const void *lab, int item, int64_t D, int64_t H, int64_t W, void *work, int64_t work_bytes,
+                            int32_t *row_offsets, void *stream);
+int64_t emp_label_measure_work_bytes(int64_t n_runs);
+int emp_label_measure(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
+                      int64_t z_base, const int32_t *row_offsets, int64_t n_runs, void *work, int64_t work_bytes,
+                      int64_t *out_table, int32_t *n_out, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38

@@ -9,7 +9,11 @@ two device synchronisations.  One JSON line.
 
     python tools/bench_infer_volume.py --size 512 [--model pdl_r50|mitonet_pr] [--axes xy,xz,yz] [--paths plain,pipeline]
                                        [--repeats 3] [--warmup 1] [--no-tune] [--no-graph] [--overlap auto|on|off]
-                                       [--window-slices W|auto] [--pyramid L] [--compressor zlib]
+                                       [--window-slices W|auto] [--pyramid L] [--compressor zlib] [--measure]
+
+--measure times every path named a second time as '<path>+measure', the same call with measure=True (per-object table,
+csrc/emp_measure.hip), on the same engine and in the same alternation: the path without it, which launches nothing new,
+is the comparison (profiles/label_measure.md).
 
 --window-slices streams every plane through windows of W slices (inference/windowed.py) on the paths named; the row then
 holds the steps per plane and the bytes of head buffers held (profiles/windowed_planes.md).
@@ -96,6 +100,7 @@ def main():
     ap.add_argument('--window-slices', default=None, help="slices per window, or 'auto'; default: whole planes")
     ap.add_argument('--pyramid', type=int, default=None, help='levels of a (2, 2, 2) label pyramid to add')
     ap.add_argument('--compressor', default=None, choices=['zlib'])
+    ap.add_argument('--measure', action='store_true', help="also time every path with measure=True, as '<path>+measure'")
     ap.add_argument('--out', default=None, help='write the JSON line to this file as well')
     args = ap.parse_args()
     _hip.require_gpu()
@@ -125,24 +130,29 @@ def main():
         # one engine per path: the plain path keeps every call site on its default, as a caller without pipeline= has it,
         # while the pipeline tunes its own engine's sites.  Per path: warm-up calls, one call for the peak memory; then
         # the timed calls of the paths ALTERNATE, so that whatever else the host and the device do hits both alike
-        for path in paths:
+        for path in list(paths):
             engine = build_engine(args.model)
             if path == 'plain':
-                fns[path] = lambda e=engine: infer_volume(e, dv, batch_pixels=args.batch_pixels, **kw)
+                call = lambda e=engine, **more: infer_volume(e, dv, batch_pixels=args.batch_pixels, **kw, **more)
             else:
                 tune = False if args.no_tune else (args.load_tune or True)
                 pipe = VolumePipeline(engine, tune=tune, graph=not args.no_graph,
                                       overlap={'auto': 'auto', 'on': True, 'off': False}[args.overlap],
                                       batch_pixels=args.batch_pixels)
-                fns[path] = lambda e=engine: infer_volume(e, dv, pipeline=pipe, **kw)
-            warm = [round(timed(fns[path])[0], 3) for _ in range(args.warmup)]
-            torch.cuda.empty_cache()
-            torch.cuda.reset_peak_memory_stats()
-            before = torch.cuda.memory_allocated()
-            timed(fns[path])
-            row[path] = {'warmup_s': warm, 'seconds': [],
-                         'peak_allocated_GiB': round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
-                         'allocated_before_call_GiB': round(before / 2 ** 30, 3)}
+                call = lambda e=engine, **more: infer_volume(e, dv, pipeline=pipe, **kw, **more)
+            fns[path] = call
+            if args.measure:
+                fns[path + '+measure'] = lambda c=call: c(measure=True)
+                paths.insert(paths.index(path) + 1, path + '+measure')
+            for name in (path, path + '+measure') if args.measure else (path,):
+                warm = [round(timed(fns[name])[0], 3) for _ in range(args.warmup)]
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                timed(fns[name])
+                row[name] = {'warmup_s': warm, 'seconds': [],
+                             'peak_allocated_GiB': round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
+                             'allocated_before_call_GiB': round(before / 2 ** 30, 3)}
         for _ in range(args.repeats):
             for path in paths:
                 t, last[path] = timed(fns[path])
@@ -153,6 +163,7 @@ def main():
                               'spread_s': round(max(times) - min(times), 4),
                               'Mvox_per_s': round(args.size ** 3 / sorted(times)[len(times) // 2] / 1e6, 2),
                               'instances': int(res['instances'][1]),
+                              'object_rows': None if 'objects' not in res else int(res['objects'][1].shape[0]),
                               'windows': res.get('windows'), 'head_bytes': res.get('head_bytes'),
                               'labelled_share': round(float((res['volumes'][1].view(torch.int32) != 0).float().mean()), 5)})
         if pipe is not None:
