@@ -121,6 +121,9 @@ SIGNATURES = {
     'emp_label_measure_count': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _P]),
     'emp_label_measure_work_bytes': (_L, [_L]),
     'emp_label_measure': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
+    'emp_label_components_work_bytes': (_L, [_L]),
+    'emp_label_components': (_I, [_P, _I, _L, _L, _L, _I, _L, _P, _L, _P, _L, _P, _P, _P]),
+    'emp_label_components_paint': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _L, _P, _I, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -791,6 +794,216 @@ def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, in
         return tables[0]
     from .measurements import merge_tables
     return merge_tables(tables)
+
+
+COMPONENTS_MAX_VOXELS = MEASURE_MAX_VOXELS   # voxels per emp_label_components call, as for its siblings
+COMPONENT_COLUMNS = 9
+
+
+def _components_operand(what, t, dtypes, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"label_components: {what} must be a tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"label_components: {what} has dtype {t.dtype}, expected one of {dtypes}")
+    if not t.is_contiguous():
+        raise ValueError(f"label_components: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"label_components: {what} is on {t.device}, expected {device}")
+    return t
+
+
+class LabelComponents:
+    """What _hip.label_components returns: `table`, the (n, 9) int64 component table on the slab's device
+    (components.COLUMNS), and paint().  It keeps the run tables of the slab's blocks on the device, and the slab itself."""
+
+    def __init__(self, slab, connectivity, table, blocks):
+        self.slab, self.connectivity, self.table, self._blocks = slab, connectivity, table, blocks
+
+    @property
+    def n(self):
+        return int(self.table.shape[0])
+
+    def paint(self, lut, out=None, dtype=None, z_range=None):
+        """Write lut[k] over the voxels of component k (lut: n values, 0 = erase; a tensor on the slab's device or
+        anything numpy converts).  out=None: a fresh (D, H, W) tensor of `dtype` (None: the slab's), background 0.
+        out=the slab itself: in place, only the voxels of runs whose value changes are written.  Any other `out` is a
+        contiguous (D, H, W) uint8 or int32 / uint32 tensor on the slab's device that does not overlap the slab; its
+        painted slices are written whole.  z_range=(z_lo, z_hi): those slices alone, the others of `out` stay as they
+        are.  A value that the output's item size cannot hold is a ValueError before anything is written, and so is
+        every other argument error.  The slab must not have changed since label_components."""
+        import numpy as np
+        slab = self.slab
+        D, H, W = (int(s) for s in slab.shape)
+        dev = slab.device
+        if isinstance(lut, torch.Tensor):
+            if lut.dtype not in (torch.uint32, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"paint: lut has dtype {lut.dtype}, expected an integer tensor")
+            lut_dev = lut.to(dev)
+            wide = lut_dev.view(torch.int32).long() & 0xffffffff if lut_dev.dtype == torch.uint32 else lut_dev.long()
+        else:
+            arr = np.asarray(lut)
+            if arr.dtype.kind not in 'iu':
+                raise ValueError(f"paint: lut has dtype {arr.dtype}, expected integers")
+            wide = torch.from_numpy(arr.astype(np.int64).reshape(-1)).to(dev)
+        if wide.dim() != 1 or wide.numel() != self.n:
+            raise ValueError(f"paint: lut has shape {tuple(wide.shape)}, the table has {self.n} components")
+        if out is None:
+            odt = slab.dtype if dtype is None else dtype
+            if odt not in (torch.uint8, torch.int32, torch.uint32):
+                raise ValueError(f"paint: dtype must be torch.uint8, int32 or uint32, got {odt}")
+        else:
+            if dtype is not None and dtype != out.dtype:
+                raise ValueError(f"paint: dtype={dtype} given together with an out of {out.dtype}")
+            _components_operand("out", out, (torch.uint8, torch.int32, torch.uint32), dev)
+            if tuple(out.shape) != (D, H, W):
+                raise ValueError(f"paint: out is {tuple(out.shape)}, the slab {(D, H, W)}")
+            odt = out.dtype
+        item = 1 if odt == torch.uint8 else 4
+        same = out is not None and out.data_ptr() == slab.data_ptr() and item == slab.element_size()
+        if out is not None and not same and slab.numel():
+            a0, b0 = slab.data_ptr(), out.data_ptr()
+            if a0 < b0 + out.numel() * item and b0 < a0 + slab.numel() * slab.element_size():
+                raise ValueError("paint: out overlaps the slab without being the slab itself")
+        z_lo, z_hi = (0, D) if z_range is None else (int(z_range[0]), int(z_range[1]))
+        if not 0 <= z_lo <= z_hi <= D:
+            raise ValueError(f"paint: z_range {z_range!r} outside 0 .. {D}")
+        top = 255 if item == 1 else 0xffffffff
+        if wide.numel() and (int(wide.min()) < 0 or int(wide.max()) > top):
+            raise ValueError(f"paint: the lut holds values outside 0 .. {top}, which a {item}-byte output cannot hold")
+        if out is None:
+            out = torch.zeros((D, H, W), dtype=odt, device=dev)
+        if slab.numel() == 0 or z_lo == z_hi:
+            return out
+        require_gpu()
+        self._paint_window(_low32(wide), z_lo, z_hi, out[z_lo:z_hi], item)
+        return out
+
+    def paint_slice(self, lut, z):
+        """slice z alone painted with lut (n int64 values on the slab's device, below 2^32) as an (H, W) uint32 plane,
+        background 0: what a seam between blocks or ranks needs of provisional ids"""
+        D, H, W = (int(s) for s in self.slab.shape)
+        if not 0 <= z < D or lut.numel() != self.n:
+            raise ValueError(f"paint_slice: slice {z} of {D}, {lut.numel()} values for {self.n} components")
+        plane = torch.zeros((1, H, W), dtype=torch.uint32, device=self.slab.device)
+        require_gpu()
+        self._paint_window(_low32(lut), z, z + 1, plane, 4)
+        return plane[0]
+
+    def _paint_window(self, lut32, z_lo, z_hi, window, item):
+        """window: the (z_hi - z_lo, H, W) tensor that receives slices [z_lo, z_hi), block by block"""
+        slab = self.slab
+        H, W = int(slab.shape[1]), int(slab.shape[2])
+        with torch.cuda.device(slab.device):
+            for b in self._blocks:
+                lo, hi = max(z_lo, b['z0']), min(z_hi, b['z1'])
+                if lo >= hi:
+                    continue
+                n_comp = int(b['index'].numel())
+                blut = lut32[b['index']].contiguous() if n_comp else None
+                work = b['work']
+                call('emp_label_components_paint', _ptr(slab[b['z0']:b['z1']]), slab.element_size(), b['z1'] - b['z0'],
+                     H, W, _ptr(b['offs']), b['n_runs'], _ptr(work), 0 if work is None else work.numel(), _ptr(blut),
+                     n_comp, lo - b['z0'], hi - b['z0'], _ptr(window[lo - z_lo:hi - z_lo]), item, _current_stream(),
+                     alg_bytes=(hi - lo) * H * W * item)
+
+
+def _low32(wide):
+    """int64 values in 0 .. 2^32 - 1 as the int32 tensor with the same low 32 bits"""
+    return (wide - ((wide >> 31) << 32)).to(torch.int32)
+
+
+def label_components(slab, connectivity=26, z_base=0, block_voxels=None, info=None):
+    """3D connected components of a label slab (emp_label_components; the definition is in include/emp_hip.h, E3): a
+    LabelComponents whose `table` is the (n, 9) int64 table on the slab's device, one row per component of equal
+    non-zero label under 6-, 18- or 26-connectivity, ascending by first voxel -- label, voxels, first (flat index,
+    z_base H W added), z0 y0 x0, z1 y1 x1 (components.COLUMNS) -- and whose paint(lut) writes a value per component
+    back over the voxels.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they
+    are).  A slab of more than block_voxels voxels (None: COMPONENTS_MAX_VOXELS, the kernel's limit) is cut into
+    z-blocks of whole slices, each labelled by itself; the end slices of neighbouring blocks are painted with
+    provisional ids, components.seam_pairs finds the ids that touch and components.merge_blocks joins them, so the table
+    is that of the undivided slab.  A single slice above the limit is a ValueError, as is every other argument error,
+    before any GPU work.  An empty or all-zero slab gives a (0, 9) table.  Two host syncs per block.  info: a dict that
+    receives 'blocks', 'runs' and 'work_bytes' (largest workspace of one call)."""
+    import numbers
+    if connectivity not in (6, 18, 26) or isinstance(connectivity, bool):
+        raise ValueError(f"label_components: connectivity must be 6, 18 or 26, got {connectivity!r}")
+    slab = _components_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+    if slab.dim() != 3:
+        raise ValueError(f"label_components: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
+        raise ValueError(f"label_components: z_base must be a non-negative integer, got {z_base!r}")
+    if block_voxels is None:
+        block_voxels = COMPONENTS_MAX_VOXELS
+    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
+          or not 1 <= block_voxels <= COMPONENTS_MAX_VOXELS):
+        raise ValueError(f"label_components: block_voxels must lie in 1 .. {COMPONENTS_MAX_VOXELS}, got {block_voxels!r}")
+    stats = {} if info is None else info
+    stats.update(blocks=0, runs=0, work_bytes=0)
+    empty = torch.zeros((0, COMPONENT_COLUMNS), dtype=torch.int64, device=dev)
+    if H * W > block_voxels:
+        raise ValueError(f"label_components: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    if not slab.is_cuda:
+        raise ValueError(f"label_components: slab is on {slab.device}, expected the GPU")
+    if slab.numel() == 0:
+        return LabelComponents(slab, connectivity, empty, [])
+    require_gpu()
+    item = slab.element_size()
+    per = max(1, int(block_voxels) // (H * W))
+    blocks = []
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            part = slab[z0:z1]
+            d = z1 - z0
+            rows = d * H
+            wb = query('emp_label_measure_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_measure_count', _ptr(part), item, d, H, W, _ptr(work), wb, _ptr(offs), _current_stream(),
+                 alg_bytes=rows * W * item)
+            n_runs = int(offs[-1].item())
+            stats['blocks'] += 1
+            stats['runs'] += n_runs
+            blk = dict(z0=z0, z1=z1, offs=offs, n_runs=n_runs, work=None, table=empty, index=None)
+            blocks.append(blk)
+            if n_runs == 0:
+                continue
+            wb = query('emp_label_components_work_bytes', n_runs)
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            blk['work'] = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            table = torch.empty((n_runs, COMPONENT_COLUMNS), dtype=torch.int64, device=dev)
+            n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_components', _ptr(part), item, d, H, W, int(connectivity), int(z_base) + z0, _ptr(offs),
+                 n_runs, _ptr(blk['work']), wb, _ptr(table), _ptr(n_out), _current_stream(), alg_bytes=rows * W * item)
+            # the capacity is one row per run: keep the table only
+            blk['table'] = table[:int(n_out.item())].clone()
+        sizes = [int(b['table'].shape[0]) for b in blocks]
+        if len(blocks) == 1:
+            blocks[0]['index'] = torch.arange(sizes[0], dtype=torch.int64, device=dev)
+            return LabelComponents(slab, connectivity, blocks[0]['table'], blocks)
+        # provisional ids: 1 + position in the concatenated block tables, painted over the blocks' end slices
+        from . import components
+        base, seams = 0, []
+        for b, n in zip(blocks, sizes):
+            b['index'] = base + torch.arange(n, dtype=torch.int64, device=dev)
+            base += n
+        if base > 0xffffffff:
+            raise ValueError(f"label_components: {base} provisional components do not fit 32-bit ids")
+        tables = [b['table'] for b in blocks]
+        prov = LabelComponents(slab, connectivity, torch.cat(tables), blocks)
+        ids = 1 + torch.arange(base, dtype=torch.int64, device=dev)
+        for lo_b, hi_b in zip(blocks[:-1], blocks[1:]):
+            z = hi_b['z0']
+            if lo_b['n_runs'] and hi_b['n_runs']:
+                seams.append(components.seam_pairs(slab[z - 1], prov.paint_slice(ids, z - 1), slab[z],
+                                                   prov.paint_slice(ids, z), connectivity))
+        table, index = components.merge_blocks(tables, seams, return_index=True)
+        for b in blocks:
+            b['index'] = index[b['index']]
+        return LabelComponents(slab, connectivity, table, blocks)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

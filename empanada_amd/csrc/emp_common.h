@@ -76,6 +76,35 @@ static inline int emp_zero_count(int32_t *n_out, hipStream_t st, const char *msg
     return EMP_OK;
 }
 
+// Lock-free union-find over int32 parents (parent[i] == i: a root), for the run tables of emp_runs.hip (2D) and
+// emp_components.hip (3D).  A unite hangs the LARGER root under the smaller with one atomicMin, so a parent only ever
+// decreases, every retry follows a strictly smaller index and the root of a finished set is its smallest member --
+// with runs in raster order, the run that holds the component's first voxel.  No thread waits for another.
+#ifdef __HIPCC__
+__device__ __forceinline__ int uf_find(const int32_t *parent, int a)
+{
+    int p = parent[a];
+    while (p != a) { a = p; p = parent[a]; }
+    return a;
+}
+__device__ __forceinline__ void uf_unite(int32_t *parent, int a, int b)
+{
+    while (true) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        if (a < b) { int t = a; a = b; b = t; }
+        int old = atomicMin(&parent[a], b);  // hang the larger root under the smaller
+        if (old == a) return;
+        a = old;
+    }
+}
+#endif
+
+// emp_measure.hip: the run extraction of its rows kernel without the neighbour rows (see there)
+int emp_label_rows_extract(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
+                           int64_t n_runs, int32_t *row, int32_t *xs, int32_t *xe, uint32_t *val, void *stream);
+
 // Stream compaction of n items: launch_flags() fills flag[0..n) with 0/1, the scan turns it into output positions
 // pos[0..n] (tmp: emp_scan_tmp_elems(n) elements), launch_emit() writes the flagged items to their positions, and the
 // number of them, pos[n], is copied to *n_out.  The two callables launch one kernel each and return EMP_OK or an

@@ -44,9 +44,12 @@ struct MsRuns {
     int32_t *idx;                  // the run's own index: the value that travels through the sort
     int32_t *row, *xs, *xe;        // xe: exclusive end, made a length by ms_fix_kernel
     uint32_t *ey0, *ey1, *ez0, *ez1;  // carried exposure scans: exclusive at the start, inclusive at the end
+    uint32_t *val;                 // the label as it is, written in place of key / idx / exposures without EXPOSE
 };
 
-template <typename T, bool EXTRACT>
+// EXPOSE (the measurements) reads the four neighbour rows and carries the exposure scans; an extraction without it
+// (emp_components.hip) reads the centre row alone and records (row, xs, xe, val) per run.
+template <typename T, bool EXTRACT, bool EXPOSE = EXTRACT>
 __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab, int64_t D, int64_t H, int64_t W,
                                                       const T *__restrict__ below, const T *__restrict__ above,
                                                       int32_t *__restrict__ row_counts,
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab,
         const int shift = (int)((reinterpret_cast<uintptr_t>(src) / sizeof(T)) & 3);
         // the four neighbour rows: inside the block, the neighbour slices at its two ends, nothing outside
         const T *ym = nullptr, *yp = nullptr, *zm = nullptr, *zp = nullptr;
-        if (EXTRACT) {
+        if (EXPOSE) {
             ym = y > 0 ? src - W : nullptr;
             yp = y + 1 < H ? src + W : nullptr;
             zm = z > 0 ? src - H * W : (below ? below + y * W : nullptr);
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab,
             // only a lane that holds a non-zero voxel reads the neighbour rows, so background costs the centre row alone;
             // the four loads go out before anything waits for the next chunk
             uint32_t a[4] = {0u, 0u, 0u, 0u}, b[4] = {0u, 0u, 0u, 0u}, f[4] = {0u, 0u, 0u, 0u}, g[4] = {0u, 0u, 0u, 0u};
-            if (EXTRACT && (c[0] | c[1] | c[2] | c[3]) != 0u) {
+            if (EXPOSE && (c[0] | c[1] | c[2] | c[3]) != 0u) {
                 ms_fetch<T>(ym, x, W, a);
                 ms_fetch<T>(yp, x, W, b);
                 ms_fetch<T>(zm, x, W, f);
@@ -123,45 +126,54 @@ __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab,
             }
             if (EXTRACT) {
                 // per-voxel exposure, y in the low half and z in the high half: at most 2 each, 512 each per chunk
-                uint32_t e[4];
+                uint32_t e[4] = {0u, 0u, 0u, 0u};
+                uint32_t incl = 0u, p = 0u;
+                if (EXPOSE) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    e[j] = c[j] == 0u ? 0u
-                                      : (uint32_t)(c[j] != a[j]) + (uint32_t)(c[j] != b[j]) +
-                                            (((uint32_t)(c[j] != f[j]) + (uint32_t)(c[j] != g[j])) << 16);
-                {
+                    for (int j = 0; j < 4; ++j)
+                        e[j] = c[j] == 0u ? 0u
+                                          : (uint32_t)(c[j] != a[j]) + (uint32_t)(c[j] != b[j]) +
+                                                (((uint32_t)(c[j] != f[j]) + (uint32_t)(c[j] != g[j])) << 16);
                     const uint32_t lane_tot = e[0] + e[1] + e[2] + e[3];
-                    uint32_t incl = lane_tot;
+                    incl = lane_tot;
 #pragma unroll
                     for (int d = 1; d < 64; d <<= 1) {
                         const uint32_t t = __shfl_up(incl, d);
                         if (lane >= d) incl += t;
                     }
-                    uint32_t p = incl - lane_tot;                       // exposure of the chunk before this lane
-                    int is = obase + n_s + ps, ie = obase + n_e + pe;
+                    p = incl - lane_tot;                                // exposure of the chunk before this lane
+                }
+                int is = obase + n_s + ps, ie = obase + n_e + pe;
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (st[j]) {
-                            if (is < n_runs) {
+                for (int j = 0; j < 4; ++j) {
+                    if (st[j]) {
+                        if (is < n_runs) {
+                            r.row[is] = (int32_t)row;
+                            r.xs[is] = (int32_t)(x + j);
+                            if (EXPOSE) {
                                 r.key[is] = (uint64_t)c[j];
                                 r.idx[is] = is;
-                                r.row[is] = (int32_t)row;
-                                r.xs[is] = (int32_t)(x + j);
                                 r.ey0[is] = sy + (p & 0xffffu);
                                 r.ez0[is] = sz + (p >> 16);
+                            } else {
+                                r.val[is] = c[j];
                             }
-                            ++is;
                         }
-                        p += e[j];
-                        if (en[j]) {
-                            if (ie < n_runs) {
-                                r.xe[ie] = (int32_t)(x + j + 1);
+                        ++is;
+                    }
+                    p += e[j];
+                    if (en[j]) {
+                        if (ie < n_runs) {
+                            r.xe[ie] = (int32_t)(x + j + 1);
+                            if (EXPOSE) {
                                 r.ey1[ie] = sy + (p & 0xffffu);
                                 r.ez1[ie] = sz + (p >> 16);
                             }
-                            ++ie;
                         }
+                        ++ie;
                     }
+                }
+                if (EXPOSE) {
                     const uint32_t chunk_tot = __shfl(incl, 63);
                     sy += chunk_tot & 0xffffu;                          // at most 2 W < 2^32 over a row
                     sz += chunk_tot >> 16;
@@ -347,11 +359,11 @@ static MsCountWork ms_count_carve(void *work, int64_t R)
 }
 extern "C" int64_t emp_label_measure_count_work_bytes(int64_t R) { return ms_count_carve(nullptr, R).total; }
 
-template <typename T, bool EXTRACT>
+template <typename T, bool EXTRACT, bool EXPOSE = EXTRACT>
 static int ms_launch(const void *lab, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
                      int32_t *row_counts, const int32_t *row_offsets, int64_t n_runs, const MsRuns &r, hipStream_t st)
 {
-    EMP_LAUNCH((ms_rows_kernel<T, EXTRACT>), emp_grid(D * H * 64, 256, 16384), 256, st, reinterpret_cast<const T *>(lab),
+    EMP_LAUNCH((ms_rows_kernel<T, EXTRACT, EXPOSE>), emp_grid(D * H * 64, 256, 16384), 256, st, reinterpret_cast<const T *>(lab),
                D, H, W, reinterpret_cast<const T *>(below), reinterpret_cast<const T *>(above), row_counts, row_offsets,
                n_runs, r);
     return EMP_OK;
@@ -376,6 +388,21 @@ extern "C" int emp_label_measure_count(const void *lab, int item, int64_t D, int
                        : ms_launch<uint8_t, false>(lab, D, H, W, nullptr, nullptr, L.counts, nullptr, 0, none, st);
     if (rc != EMP_OK) return rc;
     return emp_exclusive_scan_i32(L.counts, R, row_offsets, L.scantmp, stream);
+}
+
+// The runs of step 1's definition as (row, x start, exclusive x end, label) at row_offsets[row] + position in the row,
+// for emp_components.hip: the same kernel without the neighbour rows.  The caller has checked the shape.
+int emp_label_rows_extract(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
+                           int64_t n_runs, int32_t *row, int32_t *xs, int32_t *xe, uint32_t *val, void *stream)
+{
+    MsRuns r = {};
+    r.row = row;
+    r.xs = xs;
+    r.xe = xe;
+    r.val = val;
+    hipStream_t st = emp_stream(stream);
+    return item == 4 ? ms_launch<uint32_t, true, false>(lab, D, H, W, nullptr, nullptr, nullptr, row_offsets, n_runs, r, st)
+                     : ms_launch<uint8_t, true, false>(lab, D, H, W, nullptr, nullptr, nullptr, row_offsets, n_runs, r, st);
 }
 
 // ------------------------------------------------------------------------------------------ extract + sort + reduce

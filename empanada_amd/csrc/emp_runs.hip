@@ -280,24 +280,7 @@ extern "C" int64_t emp_runs_label_work_elems(int64_t n_runs)
     return label_carve(nullptr, n_runs > 0 ? n_runs : 1).total;
 }
 
-__device__ __forceinline__ int uf_find(const int32_t *parent, int a)
-{
-    int p = parent[a];
-    while (p != a) { a = p; p = parent[a]; }
-    return a;
-}
-__device__ __forceinline__ void uf_unite(int32_t *parent, int a, int b)
-{
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(&parent[a], b);  // hang the larger root under the smaller
-        if (old == a) return;
-        a = old;
-    }
-}
+// uf_find / uf_unite: emp_common.h (shared with emp_components.hip)
 
 __device__ __forceinline__ bool class_is_cc(uint32_t val, int64_t div, uint32_t cc_mask)
 {

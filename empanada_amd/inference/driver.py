@@ -263,18 +263,40 @@ def object_dataset_names(labels, class_names):
     return {c: f"{(class_names or {}).get(c, c)}_objects" for c in labels}
 
 
-def _neighbour_slices(slab, group):
-    """(below, above) of a rank's slab: the last slice of the nearest rank below and the first slice of the nearest
-    rank above that hold any slice, None at the volume's ends -- one gather of every rank's two end slices"""
-    rank, world = sharded._world(group)
-    if world == 1:
-        return None, None
-    bits = slab.view(torch.int32) if slab.dtype == torch.uint32 else slab      # torch copies few uint32 tensors
-    ends = torch.stack([bits[0], bits[-1]]) if bits.shape[0] else bits[:0]
-    parts = [p.view(slab.dtype) if p.dtype != slab.dtype else p for p in sharded._gather_var(ends.contiguous(), group)]
-    below = next((parts[r][1] for r in range(rank - 1, -1, -1) if parts[r].shape[0]), None)
-    above = next((parts[r][0] for r in range(rank + 1, world) if parts[r].shape[0]), None)
-    return (None if below is None else below.contiguous()), (None if above is None else above.contiguous())
+_neighbour_slices = sharded.neighbour_slices
+
+
+def _check_split(split_objects):
+    """infer_volume's `split_objects` argument -> None or the connectivity, before any GPU work"""
+    if split_objects is None:
+        return None
+    if isinstance(split_objects, (bool, np.bool_)) or not isinstance(split_objects, (int, np.integer)) \
+            or int(split_objects) not in (6, 18, 26):
+        raise ValueError(f"split_objects must be None or a connectivity of 6, 18 or 26, got {split_objects!r}")
+    return int(split_objects)
+
+
+def _splitting(finish, connectivity, thing_list, min_size, min_span, group, stats):
+    """`finish` with the repair behind it: every thing class's slab goes through components.split_volume in place, with
+    the call's min_size / min_span judged per piece, before anything reads the volumes; the counts become the objects
+    that remain and `stats` receives {class: split_volume's stats}"""
+    if connectivity is None:
+        return finish
+    from ..components import split_volume
+
+    def split_finish(planes):
+        vols, (z0, z1), counts = finish(planes)
+        counts = dict(counts)
+        for c in vols:
+            if c not in thing_list:
+                continue
+            if not vols[c].is_contiguous():
+                vols[c] = vols[c].contiguous()
+            _, stats[c] = split_volume(vols[c], connectivity, min_size, min_span, group=group, z_base=int(z0))
+            counts[c] = stats[c]['objects_out']
+        return vols, (z0, z1), counts
+
+    return split_finish
 
 
 def _measured(res, spacing, labels, class_names, out, group):
@@ -350,7 +372,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None):
+                 measure=None, split_objects=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -401,12 +423,20 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     '<class name>_objects' per class (int64, (n, 14), one raw chunk), the group's attributes gain 'objects':
     {'columns', 'spacing'} beside what they hold, and the result gains 'object_datasets': {class: array, or None where
     the store cannot hold the zero-row table of a class without objects}.
+    split_objects: None = the volumes as the consensus (or the stack's tracks) painted them, where an instance id need not
+    be one piece; 6, 18 or 26 = every thing class's slab is split into its connected components of that connectivity on
+    the device (components.split_volume; include/emp_hip.h, E3) before anything else reads it: the largest piece of an
+    id keeps the id, every further piece gets a new id above the largest, and every piece on its own must pass
+    min_size / min_span or is erased.  Datasets, compressed output, pyramid, scores and measurements see the repaired
+    labels; stuff classes stay as they are.  'instances' become the objects that remain and the result gains 'split':
+    {class: {'objects_in', 'objects_split', 'pieces_added', 'pieces_removed', 'objects_out'}}, the same on every rank.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
     window_slices = _check_windows(window_slices, mem_budget, pipeline, world)
     _check_compressor(compressor, out)
     spacing = _check_measure(measure)
+    connectivity = _check_split(split_objects)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -456,11 +486,19 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                                                   bypass, min_size, min_span, group=group)
         return vols, zs, {c: int(cons[c].alive.sum()) for c in labels}
 
+    split = {}
+    finish = _splitting(finish, connectivity, thing_list, min_size, min_span, group, split)
+
+    def done(res):
+        if connectivity is not None:
+            res['split'] = split
+        return _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
+
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,
                            track=track, finish=finish, class_names=class_names, out=out, window_slices=window_slices,
                            compressor=compressor, levels=levels)
-        return _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
+        return done(res)
     planes, base = {}, 0
     windows = {'windows': {}, 'head_bytes': 0}
     for axis in axes:
@@ -500,6 +538,5 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                     extra['pyramid_compressed_bytes'][c].append(ds.write_slab_device(lv['z_range'][0], slab)[1])
         if out is not None and rank == 0:
             write_multiscales(out, labels, class_names, levels)
-    res = _scored(result(vols, (z0, z1), counts, datasets, compressed=compressed, pyramid=extra,
-                         **(windows if window_slices is not None else {})), ground_truth, thing_list, group)
-    return _measured(res, spacing, labels, class_names, out, group)
+    return done(result(vols, (z0, z1), counts, datasets, compressed=compressed, pyramid=extra,
+                       **(windows if window_slices is not None else {})))

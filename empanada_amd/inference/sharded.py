@@ -151,6 +151,20 @@ def _gather_var(t, group=None):
     return [out[r * mx:r * mx + counts[r]].to(dev) for r in range(world)]
 
 
+def neighbour_slices(slab, group=None):
+    """(below, above) of a rank's (d, H, W) slab: the last slice of the nearest rank below and the first slice of the
+    nearest rank above that hold any slice, None at the volume's ends -- one gather of every rank's two end slices"""
+    rank, world = _world(group)
+    if world == 1:
+        return None, None
+    bits = slab.view(torch.int32) if slab.dtype == torch.uint32 else slab      # torch copies few uint32 tensors
+    ends = torch.stack([bits[0], bits[-1]]) if bits.shape[0] else bits[:0]
+    parts = [p.view(slab.dtype) if p.dtype != slab.dtype else p for p in _gather_var(ends.contiguous(), group)]
+    below = next((parts[r][1] for r in range(rank - 1, -1, -1) if parts[r].shape[0]), None)
+    above = next((parts[r][0] for r in range(rank + 1, world) if parts[r].shape[0]), None)
+    return (None if below is None else below.contiguous()), (None if above is None else above.contiguous())
+
+
 def _all_reduce_sum(a, group=None):
     """int64 numpy vector summed over the ranks"""
     rank, world = _world(group)

@@ -713,6 +713,49 @@ int emp_label_measure(const void *lab, int item, int64_t D, int64_t H, int64_t W
                       int64_t z_base, const int32_t *row_offsets, int64_t n_runs, void *work, int64_t work_bytes,
                       int64_t *out_table, int32_t *n_out, void *stream);
 
+/* ---- E3: 3D connected components of a label volume, and painting a value per component ------------------------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact: cc3d.connected_components (the
+ *          multi-label rule) and cc3d.dust; the reference itself never checks that an instance is one piece.
+ * lab is a contiguous (D, H, W) array of item-byte unsigned little-endian integers, item = 1 (uint8) or 4 (uint32; the
+ * bits of an int32 are taken as they are), 0 = background.  connectivity is 6, 18 or 26: two voxels are neighbours when
+ * their indices differ by at most 1 on every axis and on exactly one axis (6), at most two (18), any number (26).  Two
+ * voxels belong to one component when they carry the same non-zero value and a chain of neighbours of that value joins
+ * them; voxels of different values never join.  Components are numbered k = 0 .. n - 1 ascending by the flat index
+ * (z H + y) W + x of their first voxel in raster order.  The table has one row of 9 int64 per component, in that order:
+ *     0        label (the value)
+ *     1        voxels
+ *     2        first: flat index of the first voxel, with z_base H W added
+ *     3..5     z0, y0, x0   smallest index per axis, z counted as z_base + local z
+ *     6..8     z1, y1, x1   largest index + 1
+ * Sets are joined by integer atomicMin on run indices and the columns are integer sums, minima and maxima, so no
+ * visiting order, atomic order or launch shape shows in any output.
+ * Step 1  emp_label_measure_count (E2): the run count of E3 is E2's -- maximal runs of one non-zero label per row.
+ * Step 2  emp_label_components: runs -> (row, x start, x end, label) -> union-find over the runs -> roots numbered by
+ *         first run -> voxels and boxes per component.  A run searches the rows (z, y - 1) and (z - 1, y), and for 18 /
+ *         26 also (z - 1, y - 1) and (z - 1, y + 1), for runs of its own label whose x range overlaps its own; the
+ *         range is widened by one voxel on either side where the connectivity allows the step along x on top: for the
+ *         first two rows from 18 on, for the last two for 26 alone.  out_table (n_runs, 9) int64 receives n_out (device
+ *         int32[1]) rows; the runs and their component index stay in `work` (emp_label_components_work_bytes(n_runs)
+ *         bytes) for step 3.  The labels must not have changed since step 1.
+ * Step 3  emp_label_components_paint: dst, a contiguous (z_hi - z_lo, H, W) array of dst_item (1 or 4) bytes per voxel,
+ *         receives lut[component] (uint32, n_comp entries, 0 = erase) over every run's voxels of slices [z_lo, z_hi).
+ *         If dst is those slices of lab themselves (same address, same item size) only run voxels are written, and only
+ *         those of runs whose value changes; any other dst must not overlap lab and has its background written as 0.
+ *         lab, row_offsets, n_runs and work are those of step 2; lab is not read.  The low dst_item bytes of a value are
+ *         written: the caller refuses a lut with a value above 255 for dst_item 1 before the call (_hip does, and
+ *         nothing is written).  16-byte stores where a run covers a whole 16-byte group, element stores at its ends.
+ * A call covers at most 2^31 - 1 voxels (D * H * W), as for E1 / E2: a larger block is refused with EMP_EINVAL --
+ * callers cut the slab into z-blocks, label each by itself and join the blocks' components across the seams on the
+ * host (_hip.label_components, components.merge_blocks).  Step 2 reads every voxel once; step 3 writes the voxels of
+ * the runs it paints (and the background once where dst is not lab); all else is O(n_runs), all index arithmetic 64-bit. */
+int64_t emp_label_components_work_bytes(int64_t n_runs);
+int emp_label_components(const void *lab, int item, int64_t D, int64_t H, int64_t W, int connectivity, int64_t z_base,
+                         const int32_t *row_offsets, int64_t n_runs, void *work, int64_t work_bytes, int64_t *out_table,
+                         int32_t *n_out, void *stream);
+int emp_label_components_paint(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
+                               int64_t n_runs, const void *work, int64_t work_bytes, const uint32_t *lut, int64_t n_comp,
+                               int64_t z_lo, int64_t z_hi, void *dst, int dst_item, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38

@@ -24,6 +24,10 @@ same command without them is the comparison (profiles/label_pyramid.md).
 
 --split also times the forwards of the three planes alone (heads written in place, no post-processing) on the pipeline's
 own code, so that a volume whose random heads make the post-processing dominate can be read.
+
+--split 26 (or 6 / 18) also times every path with split_objects= of that connectivity, as '<path>+split', alternating
+with the path without it, and records res['split'] of class 1: how many ids were disconnected, how many pieces got a
+new id and how many were erased (profiles/label_components.md).
 """
 import argparse
 import json
@@ -96,7 +100,9 @@ def main():
     ap.add_argument('--save-tune', default=None)
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--overlap', default='auto', choices=['auto', 'on', 'off'])
-    ap.add_argument('--split', action='store_true', help='also time the forwards alone')
+    ap.add_argument('--split', nargs='?', const='forwards', default=None, choices=['forwards', '6', '18', '26'],
+                    help="bare: also time the forwards alone; 6 / 18 / 26: also time every path with split_objects= of "
+                         "that connectivity, as '<path>+split', and report what the split found")
     ap.add_argument('--window-slices', default=None, help="slices per window, or 'auto'; default: whole planes")
     ap.add_argument('--pyramid', type=int, default=None, help='levels of a (2, 2, 2) label pyramid to add')
     ap.add_argument('--compressor', default=None, choices=['zlib'])
@@ -125,6 +131,8 @@ def main():
     row = {'size': args.size, 'model': args.model, 'axes': list(axes), 'batch_pixels': args.batch_pixels,
            'window_slices': kw.get('window_slices'), 'pyramid': args.pyramid, 'compressor': args.compressor,
            'device': torch.cuda.get_device_name(0), 'repeats': args.repeats, 'warmup': args.warmup}
+    split_objects = int(args.split) if args.split not in (None, 'forwards') else None
+    row['split_objects'] = split_objects
     fns, pipe, last = {}, None, {}
     try:
         # one engine per path: the plain path keeps every call site on its default, as a caller without pipeline= has it,
@@ -141,10 +149,15 @@ def main():
                                       batch_pixels=args.batch_pixels)
                 call = lambda e=engine, **more: infer_volume(e, dv, pipeline=pipe, **kw, **more)
             fns[path] = call
+            names = [path]
             if args.measure:
                 fns[path + '+measure'] = lambda c=call: c(measure=True)
-                paths.insert(paths.index(path) + 1, path + '+measure')
-            for name in (path, path + '+measure') if args.measure else (path,):
+                names.append(path + '+measure')
+            if split_objects is not None:
+                fns[path + '+split'] = lambda c=call: c(split_objects=split_objects)
+                names.append(path + '+split')
+            paths[paths.index(path):paths.index(path) + 1] = names
+            for name in names:
                 warm = [round(timed(fns[name])[0], 3) for _ in range(args.warmup)]
                 torch.cuda.empty_cache()
                 torch.cuda.reset_peak_memory_stats()
@@ -164,13 +177,14 @@ def main():
                               'Mvox_per_s': round(args.size ** 3 / sorted(times)[len(times) // 2] / 1e6, 2),
                               'instances': int(res['instances'][1]),
                               'object_rows': None if 'objects' not in res else int(res['objects'][1].shape[0]),
+                              'split': res.get('split', {}).get(1),
                               'windows': res.get('windows'), 'head_bytes': res.get('head_bytes'),
                               'labelled_share': round(float((res['volumes'][1].view(torch.int32) != 0).float().mean()), 5)})
         if pipe is not None:
             row['pipeline']['pipeline'] = last['pipeline']['pipeline']
             if args.save_tune:
                 pipe.save_tune(args.save_tune)
-            if args.split:
+            if args.split == 'forwards':
                 row['pipeline']['forwards_only_s'] = [round(t, 4) for t in forwards_only(pipe, dv, axes, args.repeats)]
             pipe.close()
         if 'plain' in row and 'pipeline' in row:
