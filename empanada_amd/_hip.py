@@ -124,6 +124,10 @@ SIGNATURES = {
     'emp_label_components_work_bytes': (_L, [_L]),
     'emp_label_components': (_I, [_P, _I, _L, _L, _L, _I, _L, _P, _L, _P, _L, _P, _P, _P]),
     'emp_label_components_paint': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _P, _L, _L, _L, _P, _I, _P]),
+    'emp_label_holes_count_work_bytes': (_L, [_L]),
+    'emp_label_holes_count': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _P]),
+    'emp_label_holes_work_bytes': (_L, [_L]),
+    'emp_label_holes': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -1004,6 +1008,140 @@ def label_components(slab, connectivity=26, z_base=0, block_voxels=None, info=No
         for b in blocks:
             b['index'] = index[b['index']]
         return LabelComponents(slab, connectivity, table, blocks)
+
+
+HOLES_MAX_VOXELS = MEASURE_MAX_VOXELS        # voxels per emp_label_holes call, as for its siblings
+HOLE_COLUMNS = 10
+
+
+def _holes_operand(what, t, dtype=None, shape=None, device=None):
+    try:
+        _expect(f"label_holes: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if not t.is_contiguous():
+        raise ValueError(f"label_holes: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"label_holes: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+class LabelHoles(LabelComponents):
+    """What _hip.label_holes returns: `table`, the (n, 10) int64 cavity table on the slab's device (holes.COLUMNS), `n`,
+    paint() and paint_slice().  It keeps the zero-run tables of the slab's blocks on the device, in the layout of
+    LabelComponents, and the slab itself: the runs' value is 0, so emp_label_components_paint in place writes exactly
+    the runs whose lut entry is not 0."""
+
+    def __init__(self, slab, table, blocks):
+        super().__init__(slab, 6, table, blocks)
+
+    def paint(self, lut):
+        """Write lut[k] over the voxels of cavity k in the slab itself (lut: n values, 0 = leave; a tensor on the
+        slab's device or anything numpy converts); nothing but the voxels of cavities with a non-zero entry is written.
+        A value that the slab's item size cannot hold is a ValueError before anything is written.  Returns the slab.
+        The slab must not have changed since label_holes."""
+        return super().paint(lut, out=self.slab)
+
+
+def label_holes(slab, below=None, above=None, z_base=0, block_voxels=None, info=None):
+    """The background cavities of a label slab (emp_label_holes; the definition is in include/emp_hip.h, E4): a
+    LabelHoles whose `table` is the (n, 10) int64 table on the slab's device, one row per 6-connected component of the
+    zero voxels, ascending by first voxel -- voxels, first (flat index, z_base H W added), z0 y0 x0, z1 y1 x1, lab_min,
+    lab_max (holes.COLUMNS) -- whose paint(lut) writes a label per cavity over its voxels in place and whose
+    paint_slice(ids, z) gives one slice painted with ids, as a seam between ranks needs it.  slab: (D, H, W), contiguous,
+    on the GPU, uint8 or int32 / uint32 (the bits are taken as they are).  below / above: (H, W) tensors of the slab's
+    dtype and device that stand for the slices at z = -1 and z = D, None = no neighbour there; z_base is added to every
+    z index.  A slab of more than block_voxels voxels (None: HOLES_MAX_VOXELS, the kernel's limit) is cut into z-blocks
+    of whole slices, each labelled by itself with its true neighbour slices -- views of the slab, or below / above at its
+    ends; the end slices of neighbouring blocks are painted with provisional ids, components.seam_pairs finds the ids
+    that touch over zero voxels and holes.merge_blocks joins them, so the table is that of the undivided slab.  A single
+    slice above the limit is a ValueError, as is every other argument error, before any GPU work.  An empty slab or one
+    without a zero voxel gives a (0, 10) table.  Two host syncs per block.  info: a dict that receives 'blocks', 'runs'
+    and 'work_bytes' (largest workspace of one call)."""
+    import numbers
+    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
+        raise ValueError(f"label_holes: z_base must be a non-negative integer, got {z_base!r}")
+    if block_voxels is None:
+        block_voxels = HOLES_MAX_VOXELS
+    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
+          or not 1 <= block_voxels <= HOLES_MAX_VOXELS):
+        raise ValueError(f"label_holes: block_voxels must lie in 1 .. {HOLES_MAX_VOXELS}, got {block_voxels!r}")
+    slab = _holes_operand("slab", slab)
+    if slab.dim() != 3:
+        raise ValueError(f"label_holes: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if below is not None:
+        below = _holes_operand("below", below, slab.dtype, (H, W), dev)
+    if above is not None:
+        above = _holes_operand("above", above, slab.dtype, (H, W), dev)
+    stats = {} if info is None else info
+    stats.update(blocks=0, runs=0, work_bytes=0)
+    empty = torch.zeros((0, HOLE_COLUMNS), dtype=torch.int64, device=dev)
+    if H * W > block_voxels:
+        raise ValueError(f"label_holes: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    if not slab.is_cuda:
+        raise ValueError(f"label_holes: slab is on {slab.device}, expected the GPU")
+    if slab.numel() == 0:
+        return LabelHoles(slab, empty, [])
+    require_gpu()
+    item = slab.element_size()
+    per = max(1, int(block_voxels) // (H * W))
+    blocks = []
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            part = slab[z0:z1]
+            lo = below if z0 == 0 else slab[z0 - 1]
+            hi = above if z1 == D else slab[z1]
+            d = z1 - z0
+            rows = d * H
+            wb = query('emp_label_holes_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_holes_count', _ptr(part), item, d, H, W, _ptr(work), wb, _ptr(offs), _current_stream(),
+                 alg_bytes=rows * W * item)
+            n_runs = int(offs[-1].item())
+            stats['blocks'] += 1
+            stats['runs'] += n_runs
+            blk = dict(z0=z0, z1=z1, offs=offs, n_runs=n_runs, work=None, table=empty, index=None)
+            blocks.append(blk)
+            if n_runs == 0:
+                continue
+            wb = query('emp_label_holes_work_bytes', n_runs)
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            blk['work'] = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            table = torch.empty((n_runs, HOLE_COLUMNS), dtype=torch.int64, device=dev)
+            n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_holes', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), int(z_base) + z0, _ptr(offs), n_runs,
+                 _ptr(blk['work']), wb, _ptr(table), _ptr(n_out), _current_stream(), alg_bytes=rows * W * item)
+            # the capacity is one row per run: keep the table only
+            blk['table'] = table[:int(n_out.item())].clone()
+        sizes = [int(b['table'].shape[0]) for b in blocks]
+        if len(blocks) == 1:
+            blocks[0]['index'] = torch.arange(sizes[0], dtype=torch.int64, device=dev)
+            return LabelHoles(slab, blocks[0]['table'], blocks)
+        # provisional ids: 1 + position in the concatenated block tables, painted over the blocks' end slices
+        from . import components, holes
+        base, seams = 0, []
+        for b, n in zip(blocks, sizes):
+            b['index'] = base + torch.arange(n, dtype=torch.int64, device=dev)
+            base += n
+        if base > 0xffffffff:
+            raise ValueError(f"label_holes: {base} provisional cavities do not fit 32-bit ids")
+        tables = [b['table'] for b in blocks]
+        prov = LabelHoles(slab, torch.cat(tables), blocks)
+        ids = 1 + torch.arange(base, dtype=torch.int64, device=dev)
+        for lo_b, hi_b in zip(blocks[:-1], blocks[1:]):
+            z = hi_b['z0']
+            if lo_b['n_runs'] and hi_b['n_runs']:
+                seams.append(components.seam_pairs(holes._is_zero(slab[z - 1]), prov.paint_slice(ids, z - 1),
+                                                   holes._is_zero(slab[z]), prov.paint_slice(ids, z), 6))
+        table, index = holes.merge_blocks(tables, seams, return_index=True)
+        for b in blocks:
+            b['index'] = index[b['index']]
+        return LabelHoles(slab, table, blocks)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

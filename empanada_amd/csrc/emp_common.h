@@ -105,6 +105,41 @@ __device__ __forceinline__ void uf_unite(int32_t *parent, int a, int b)
 int emp_label_rows_extract(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
                            int64_t n_runs, int32_t *row, int32_t *xs, int32_t *xe, uint32_t *val, void *stream);
 
+// The run records of an emp_components.hip / emp_holes.hip call, indexed by run (row_offsets[row] + position in the
+// row); what the paint step (emp_label_components_paint) reads stays in `work`.  One layout for both files, so that the
+// runs of either can be painted.
+struct CcWork {
+    int32_t *row, *xs, *xe;        // xe: exclusive end
+    uint32_t *val;
+    int32_t *comp;                 // component index of the run (step 2's second output)
+    int32_t *parent, *flag, *pos, *scantmp;
+    int64_t keep, total;           // bytes up to and including comp; all of it
+};
+static inline CcWork cc_carve(void *work, int64_t n)
+{
+    if (n < 1) n = 1;
+    EmpCarver c(work);
+    CcWork L;
+    L.row = c.take<int32_t>(n);
+    L.xs = c.take<int32_t>(n);
+    L.xe = c.take<int32_t>(n);
+    L.val = c.take<uint32_t>(n);
+    L.comp = c.take<int32_t>(n);
+    L.keep = c.bytes();
+    L.parent = c.take<int32_t>(n);
+    L.flag = c.take<int32_t>(n);
+    L.pos = c.take<int32_t>(n + 1);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(n));
+    L.total = c.bytes();
+    return L;
+}
+
+// emp_components.hip: the union-find over the runs of L (equal `val`, connectivity 6, 18 or 26) and, after it, the
+// flattening that leaves parent[i] = root and flag[i] = (i is a root); one or two launches each
+int emp_cc_unite(const CcWork &L, int64_t n_runs, int64_t H, int64_t n_rows, int connectivity,
+                 const int32_t *row_offsets, void *stream);
+int emp_cc_roots(const CcWork &L, int64_t n_runs, void *stream);
+
 // Stream compaction of n items: launch_flags() fills flag[0..n) with 0/1, the scan turns it into output positions
 // pos[0..n] (tmp: emp_scan_tmp_elems(n) elements), launch_emit() writes the flagged items to their positions, and the
 // number of them, pos[n], is copied to *n_out.  The two callables launch one kernel each and return EMP_OK or an

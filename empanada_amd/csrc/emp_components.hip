@@ -12,32 +12,6 @@
 
 #define CC_COLS 9
 
-// the run records of a call, indexed by run (row_offsets[row] + position in the row); what step 3 reads stays in `work`
-struct CcWork {
-    int32_t *row, *xs, *xe;        // xe: exclusive end
-    uint32_t *val;
-    int32_t *comp;                 // component index of the run (step 2's second output)
-    int32_t *parent, *flag, *pos, *scantmp;
-    int64_t keep, total;           // bytes up to and including comp; all of it
-};
-static CcWork cc_carve(void *work, int64_t n)
-{
-    if (n < 1) n = 1;
-    EmpCarver c(work);
-    CcWork L;
-    L.row = c.take<int32_t>(n);
-    L.xs = c.take<int32_t>(n);
-    L.xe = c.take<int32_t>(n);
-    L.val = c.take<uint32_t>(n);
-    L.comp = c.take<int32_t>(n);
-    L.keep = c.bytes();
-    L.parent = c.take<int32_t>(n);
-    L.flag = c.take<int32_t>(n);
-    L.pos = c.take<int32_t>(n + 1);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(n));
-    L.total = c.bytes();
-    return L;
-}
 extern "C" int64_t emp_label_components_work_bytes(int64_t n_runs) { return cc_carve(nullptr, n_runs).total; }
 
 __global__ void cc_init_kernel(int64_t n, int32_t *__restrict__ parent)
@@ -98,6 +72,24 @@ __global__ void cc_flatten_kernel(int64_t n, int32_t *parent, int32_t *__restric
         // roots do not change any more, so writing the root is race-free with the finds of other threads
         if (r != (int)i) parent[i] = r;
     }
+}
+
+// the two halves of the union-find as launches, for this file and for emp_holes.hip (whose runs all carry value 0)
+int emp_cc_unite(const CcWork &L, int64_t n_runs, int64_t H, int64_t n_rows, int connectivity,
+                 const int32_t *row_offsets, void *stream)
+{
+    hipStream_t st = emp_stream(stream);
+    const int grid = emp_grid(n_runs, 256, 4096);
+    EMP_LAUNCH(cc_init_kernel, grid, 256, st, n_runs, L.parent);
+    EMP_LAUNCH(cc_union_kernel, grid, 256, st, n_runs, H, n_rows, connectivity, L.row, L.xs, L.xe, L.val, row_offsets,
+               L.parent);
+    return EMP_OK;
+}
+
+int emp_cc_roots(const CcWork &L, int64_t n_runs, void *stream)
+{
+    EMP_LAUNCH(cc_flatten_kernel, emp_grid(n_runs, 256, 4096), 256, emp_stream(stream), n_runs, L.parent, L.flag);
+    return EMP_OK;
 }
 
 // pos[root] numbers the roots in run order; the root's own thread starts the component's row
@@ -181,15 +173,11 @@ extern "C" int emp_label_components(const void *lab, int item, int64_t D, int64_
     int rc = emp_label_rows_extract(lab, item, D, H, W, row_offsets, n_runs, L.row, L.xs, L.xe, L.val, stream);
     if (rc != EMP_OK) return rc;
     const int grid = emp_grid(n_runs, 256, 4096);
-    EMP_LAUNCH(cc_init_kernel, grid, 256, st, n_runs, L.parent);
-    EMP_LAUNCH(cc_union_kernel, grid, 256, st, n_runs, H, D * H, connectivity, L.row, L.xs, L.xe, L.val, row_offsets,
-               L.parent);
+    rc = emp_cc_unite(L, n_runs, H, D * H, connectivity, row_offsets, stream);
+    if (rc != EMP_OK) return rc;
     rc = emp_compact(
         L.flag, n_runs, L.pos, L.scantmp, n_out, stream, "label_components: count copy",
-        [&]() -> int {
-            EMP_LAUNCH(cc_flatten_kernel, grid, 256, st, n_runs, L.parent, L.flag);
-            return EMP_OK;
-        },
+        [&]() -> int { return emp_cc_roots(L, n_runs, stream); },
         [&]() -> int {
             EMP_LAUNCH(cc_comp_kernel, grid, 256, st, n_runs, W, z_base * H * W, L.parent, L.flag, L.pos, L.row, L.xs,
                        L.val, L.comp, out_table);

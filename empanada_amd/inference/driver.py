@@ -299,6 +299,38 @@ def _splitting(finish, connectivity, thing_list, min_size, min_span, group, stat
     return split_finish
 
 
+def _check_fill(fill_holes):
+    """infer_volume's `fill_holes` argument -> (wanted, cap in voxels or None), before any GPU work"""
+    if fill_holes is None:
+        return False, None
+    if fill_holes is True:
+        return True, None
+    if isinstance(fill_holes, (bool, np.bool_)) or not isinstance(fill_holes, (int, np.integer)) or int(fill_holes) < 1:
+        raise ValueError("fill_holes must be None, True or a positive number of voxels (the largest cavity to fill), "
+                         f"got {fill_holes!r}")
+    return True, int(fill_holes)
+
+
+def _filling(finish, wanted, max_voxels, thing_list, shape3d, group, stats):
+    """`finish` with the filling behind it: every thing class's slab goes through holes.fill_volume in place before
+    anything reads the volumes; objects only grow, so the counts stay, and `stats` receives {class: fill_volume's stats}"""
+    if not wanted:
+        return finish
+    from ..holes import fill_volume
+
+    def fill_finish(planes):
+        vols, (z0, z1), counts = finish(planes)
+        for c in vols:
+            if c not in thing_list:
+                continue
+            if not vols[c].is_contiguous():
+                vols[c] = vols[c].contiguous()
+            _, stats[c] = fill_volume(vols[c], shape3d, max_voxels, group=group, z_base=int(z0))
+        return vols, (z0, z1), counts
+
+    return fill_finish
+
+
 def _measured(res, spacing, labels, class_names, out, group):
     """the result with 'objects': every rank measures its slab of every class (_hip.measure_labels, z_base = z0) with the
     neighbouring ranks' end slices standing for what lies outside it, the tables are merged over the ranks, and rank 0
@@ -372,7 +404,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None, split_objects=None):
+                 measure=None, split_objects=None, fill_holes=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -430,6 +462,14 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     min_size / min_span or is erased.  Datasets, compressed output, pyramid, scores and measurements see the repaired
     labels; stuff classes stay as they are.  'instances' become the objects that remain and the result gains 'split':
     {class: {'objects_in', 'objects_split', 'pieces_added', 'pieces_removed', 'objects_out'}}, the same on every rank.
+    fill_holes: None = the volumes as they are; True = in every thing class's slab every closed cavity -- a 6-connected
+    component of background voxels that does not reach the border of the volume -- whose wall carries ONE label is
+    painted with that label on the device (holes.fill_volume; include/emp_hip.h, E4), right after split_objects and
+    before anything else reads the slab; a positive integer fills only the cavities of at most that many voxels.  A
+    cavity walled by two or more labels (a gap between touching objects, the shell around a nested object) is left.
+    Datasets, compressed output, pyramid, scores and measurements see the filled labels; stuff classes stay as they
+    are and 'instances' do not change.  The result gains 'filled': {class: {'cavities', 'filled', 'voxels_filled',
+    'shared', 'too_large'}}, the same on every rank.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -437,6 +477,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     _check_compressor(compressor, out)
     spacing = _check_measure(measure)
     connectivity = _check_split(split_objects)
+    fill_wanted, fill_cap = _check_fill(fill_holes)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -488,10 +529,14 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
 
     split = {}
     finish = _splitting(finish, connectivity, thing_list, min_size, min_span, group, split)
+    filled = {}
+    finish = _filling(finish, fill_wanted, fill_cap, thing_list, shape3d, group, filled)
 
     def done(res):
         if connectivity is not None:
             res['split'] = split
+        if fill_wanted:
+            res['filled'] = filled
         return _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
 
     if pipeline is not None:

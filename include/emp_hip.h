@@ -756,6 +756,68 @@ int emp_label_components_paint(const void *lab, int item, int64_t D, int64_t H, 
                                int64_t n_runs, const void *work, int64_t work_bytes, const uint32_t *lut, int64_t n_comp,
                                int64_t z_lo, int64_t z_hi, void *dst, int dst_item, void *stream);
 
+/* ---- E4: background cavities of a label volume, for filling the holes enclosed in objects ---------------------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact: scipy.ndimage.binary_fill_holes or
+ *          fill_voids object by object (the napari front-end's "fill holes in segmentation" switch).
+ * lab is a contiguous (D, H, W) array of item-byte unsigned little-endian integers, item = 1 (uint8) or 4 (uint32; the
+ * bits of an int32 are taken as they are), 0 = background.
+ *   - A cavity is a 6-connected component of the zero voxels (indices differ by 1 on exactly one axis): the complement
+ *     of 26-connected objects, so a diagonal leak does not open a cavity.
+ *   - A cavity is open if one of its voxels lies on the border of the WHOLE volume (index 0 or size - 1 on any axis),
+ *     closed otherwise.
+ *   - The wall labels of a cavity are the non-zero values of the voxels that share a FACE with one of its voxels; a
+ *     voxel that touches it only across an edge or a corner does not count.  Labels compare as unsigned 32-bit numbers.
+ *   - A closed cavity is filled with L if and only if its wall labels are exactly {L} (lab_min == lab_max == L) and,
+ *     with a cap max_voxels, voxels <= max_voxels.  A closed cavity walled by two or more labels -- a gap between
+ *     touching objects, the shell around an object nested in another -- is left alone and counted as shared.
+ * Cavities are numbered k = 0 .. n - 1 ascending by the flat index (z H + y) W + x of their first voxel in raster
+ * order.  The table has one row of 10 int64 per cavity, in that order:
+ *     0        voxels
+ *     1        first: flat index of the first voxel, with z_base H W added
+ *     2..4     z0, y0, x0   smallest index per axis, z counted as z_base + local z
+ *     5..7     z1, y1, x1   largest index + 1
+ *     8        lab_min: smallest wall label, 2^32 if none was surveyed
+ *     9        lab_max: largest wall label, 0 if none was surveyed
+ * Openness is no column: the host derives it from the box against the whole volume's shape (holes.plan), after the
+ * tables of z-blocks and ranks have been merged, so neither needs a special case.  A component whose box touches x = 0,
+ * x = W, y = 0 or y = H of the block is open whatever lies beyond the block in z: its wall is NOT surveyed and it
+ * reports (2^32, 0).  Every other component is bounded by non-zero voxels along x, so its lab_max is non-zero: lab_max
+ * == 0 is the mark "touches an x or y border", and a merge of block tables gives (2^32, 0) to every merged component
+ * that has a piece with that mark (holes.merge_blocks), which is what the undivided volume reports.  The outside
+ * background is one such component and holds most zero runs of a volume, so the survey costs in proportion to the
+ * voxels of candidate cavities, not of the volume.  Along z the block has two optional neighbour slices as in E2,
+ * `below` (z = -1) and `above` (z = D): a null pointer means "no neighbour there", and the labels of a neighbour slice
+ * over a cavity's voxels enter its wall labels (zero voxels there are the business of the seam: components.seam_pairs).
+ * Sets are joined by integer atomicMin on run indices and the columns are integer sums, minima and maxima, so no
+ * visiting order, atomic order, launch shape or z-partition shows in any output.
+ * Step 1  emp_label_holes_count: row_offsets[0..R] (R + 1 int32, R = D * H) = exclusive prefix sum of the number of
+ *         maximal runs of ZERO voxels per row; row_offsets[R] is the run total n_runs.  work:
+ *         emp_label_holes_count_work_bytes(R) bytes.
+ * Step 2  emp_label_holes: zero runs -> (row, x start, x end, 0) -> E3's union-find with connectivity 6 (rows (z, y - 1)
+ *         and (z - 1, y), x ranges overlapping, not widened) -> roots numbered by first run -> voxels and boxes, reduced
+ *         over the wave before one atomic per segment of equal component (the outside component alone holds millions
+ *         of runs) -> wall labels of the candidates: the voxels just before and after a run along x, and the voxels over
+ *         the run's x range in rows y +- 1 and z +- 1.  out_table (n_runs, 10) int64 receives n_out (device int32[1])
+ *         rows; the runs and their component index stay in `work` (emp_label_holes_work_bytes(n_runs) bytes) in E3's
+ *         layout.  The labels must not have changed since step 1.
+ * Step 3  emp_label_components_paint (E3) with lab, row_offsets, n_runs and work of step 2 and dst = the slices [z_lo,
+ *         z_hi) of lab themselves: every run's value is 0, so in place it writes lut[component] over the runs whose lut
+ *         entry is non-zero and nothing else -- nothing but voxels of filled cavities is written.
+ * A call covers at most 2^31 - 1 voxels (D * H * W), as for E2 / E3: a larger block is refused with EMP_EINVAL --
+ * callers cut the slab into z-blocks, hand each its neighbour slices and join the blocks' components across the seams
+ * on the host (_hip.label_holes, holes.merge_blocks).  Step 1 and step 2 read every voxel once (16-byte loads of uint32
+ * and 4-byte loads of uint8 per lane where the group lies on such an address, element-wise loads with the same results
+ * otherwise); the survey reads, element-wise, six neighbours' worth of the candidates' voxels; all else is O(n_runs),
+ * all index arithmetic 64-bit.  No memset node: counts and workspace are zeroed by kernels, so every step can be
+ * captured.  An empty slab and n_runs == 0 (no zero voxel) are no-ops with n_out = 0.                                 */
+int64_t emp_label_holes_count_work_bytes(int64_t R);
+int emp_label_holes_count(const void *lab, int item, int64_t D, int64_t H, int64_t W, void *work, int64_t work_bytes,
+                          int32_t *row_offsets, void *stream);
+int64_t emp_label_holes_work_bytes(int64_t n_runs);
+int emp_label_holes(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
+                    int64_t z_base, const int32_t *row_offsets, int64_t n_runs, void *work, int64_t work_bytes,
+                    int64_t *out_table, int32_t *n_out, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38

@@ -28,6 +28,9 @@ own code, so that a volume whose random heads make the post-processing dominate 
 --split 26 (or 6 / 18) also times every path with split_objects= of that connectivity, as '<path>+split', alternating
 with the path without it, and records res['split'] of class 1: how many ids were disconnected, how many pieces got a
 new id and how many were erased (profiles/label_components.md).
+
+--fill also times every path with fill_holes=True, as '<path>+fill', alternating likewise, and records res['filled'] of
+class 1: how many closed cavities there were, how many were filled, shared or too large (profiles/label_holes.md).
 """
 import argparse
 import json
@@ -103,6 +106,8 @@ def main():
     ap.add_argument('--split', nargs='?', const='forwards', default=None, choices=['forwards', '6', '18', '26'],
                     help="bare: also time the forwards alone; 6 / 18 / 26: also time every path with split_objects= of "
                          "that connectivity, as '<path>+split', and report what the split found")
+    ap.add_argument('--fill', action='store_true',
+                    help="also time every path with fill_holes=True, as '<path>+fill', and report res['filled'] of class 1")
     ap.add_argument('--window-slices', default=None, help="slices per window, or 'auto'; default: whole planes")
     ap.add_argument('--pyramid', type=int, default=None, help='levels of a (2, 2, 2) label pyramid to add')
     ap.add_argument('--compressor', default=None, choices=['zlib'])
@@ -156,6 +161,9 @@ def main():
             if split_objects is not None:
                 fns[path + '+split'] = lambda c=call: c(split_objects=split_objects)
                 names.append(path + '+split')
+            if args.fill:
+                fns[path + '+fill'] = lambda c=call: c(fill_holes=True)
+                names.append(path + '+fill')
             paths[paths.index(path):paths.index(path) + 1] = names
             for name in names:
                 warm = [round(timed(fns[name])[0], 3) for _ in range(args.warmup)]
@@ -178,6 +186,7 @@ def main():
                               'instances': int(res['instances'][1]),
                               'object_rows': None if 'objects' not in res else int(res['objects'][1].shape[0]),
                               'split': res.get('split', {}).get(1),
+                              'filled': res.get('filled', {}).get(1),
                               'windows': res.get('windows'), 'head_bytes': res.get('head_bytes'),
                               'labelled_share': round(float((res['volumes'][1].view(torch.int32) != 0).float().mean()), 5)})
         if pipe is not None:
