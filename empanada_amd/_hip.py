@@ -128,6 +128,11 @@ SIGNATURES = {
     'emp_label_holes_count': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _P]),
     'emp_label_holes_work_bytes': (_L, [_L]),
     'emp_label_holes': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P]),
+    'emp_label_edt_work_bytes': (_L, [_L, _L, _L, _L, _L]),
+    'emp_label_edt': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
+    'emp_label_erode': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
+    'emp_label_dilate_work_bytes': (_L, [_L, _L, _L, _L, _L]),
+    'emp_label_dilate': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -1142,6 +1147,161 @@ def label_holes(slab, below=None, above=None, z_base=0, block_voxels=None, info=
         for b in blocks:
             b['index'] = index[b['index']]
         return LabelHoles(slab, table, blocks)
+
+
+MORPH_MAX_VOXELS = MEASURE_MAX_VOXELS        # voxels per emp_label_edt / _erode / _dilate call, halos included
+
+
+def _morph_sampling(name, sampling):
+    import numbers
+    try:
+        vals = tuple(sampling)
+    except TypeError:
+        vals = None
+    if vals is None or len(vals) != 3 or any(isinstance(a, bool) or not isinstance(a, numbers.Integral) or
+                                             not 1 <= a <= 16 for a in vals):
+        raise ValueError(f"{name}: sampling must be three integers (az, ay, ax) in 1 .. 16, got {sampling!r}")
+    return tuple(int(a) for a in vals)
+
+
+def _morph_bound(name, what, value, lo, hi):
+    import numbers
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
+        raise ValueError(f"{name}: {what} must be an integer in {lo} .. {hi}, got {value!r}")
+    return int(value)
+
+
+def _morph_operand(name, what, t, dtype=None, shape=None, device=None):
+    try:
+        _expect(f"{name}: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype)
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if shape is not None and (t.dim() != 3 or tuple(t.shape[1:]) != tuple(shape)):
+        raise ValueError(f"{name}: {what} must be a (h, {shape[0]}, {shape[1]}) stack, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+def _morph(name, slab, sampling, bound, below, above, block_voxels, info):
+    """What label_edt, label_erode and label_dilate share: the checks, the cut into z-blocks with their halo stacks and
+    the calls.  bound: cap - 1 for the distance, r2 for the others -- floor(sqrt(bound)) // az slices are all a block
+    needs of its neighbours."""
+    import math
+    az, ay, ax = sampling = _morph_sampling(name, sampling)
+    if name == 'label_edt':
+        limit = _morph_bound(name, "cap", bound, 1, 65535)
+        bound = limit - 1
+    else:
+        limit = bound = _morph_bound(name, "r2", bound, 1, 65534)
+        if bound < min(sampling) ** 2:
+            raise ValueError(f"{name}: r2 = {bound} is below the smallest squared pitch of {sampling}: the ball is a "
+                             "point")
+    if block_voxels is not None:
+        block_voxels = _morph_bound(name, "block_voxels", block_voxels, 1, MORPH_MAX_VOXELS)
+    slab = _morph_operand(name, "slab", slab)
+    if slab.dim() != 3:
+        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if below is not None:
+        below = _morph_operand(name, "below", below, slab.dtype, (H, W), dev)
+    if above is not None:
+        above = _morph_operand(name, "above", above, slab.dtype, (H, W), dev)
+    stats = {} if info is None else info
+    stats.update(blocks=0, work_bytes=0)
+    out_dtype = torch.uint16 if name == 'label_edt' else slab.dtype
+    if slab.numel() == 0:
+        return torch.empty((D, H, W), dtype=out_dtype, device=dev)
+    halo = math.isqrt(bound) // az
+    if H * W > (MORPH_MAX_VOXELS if block_voxels is None else block_voxels):
+        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{MORPH_MAX_VOXELS if block_voxels is None else block_voxels} voxels per call; there is no "
+                         "split within a slice")
+    # block_voxels counts a block's own slices; its halo slices come on top and count towards the limit of a call
+    per = max(1, MORPH_MAX_VOXELS // (H * W) - 2 * halo) if block_voxels is None else block_voxels // (H * W)
+    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
+    for z0 in range(0, D, per):
+        z1 = min(D, z0 + per)
+        total = min(halo, z0 + n_below) + z1 - z0 + min(halo, D - z1 + n_above)
+        if total * H * W > MORPH_MAX_VOXELS:
+            raise ValueError(f"{name}: a block of {z1 - z0} slices of {H} x {W} with its halo slices is {total * H * W} "
+                             f"voxels, above the limit of {MORPH_MAX_VOXELS} voxels per call")
+    require_gpu()
+    item = slab.element_size()
+    out = torch.empty((D, H, W), dtype=out_dtype, device=dev)
+    near = name == 'label_dilate'
+
+    def stack(lo, hi, outer, at_start):
+        """the slices [lo, hi) of the slab continued by `outer`, the caller's stack beyond the slab's end"""
+        if at_start:                                          # lo may be negative: those come from the end of `outer`
+            inner = slab[max(lo, 0):hi]
+            want = -lo if lo < 0 else 0
+            extra = None if outer is None or want == 0 else outer[max(int(outer.shape[0]) - want, 0):]
+            parts = [p for p in (extra, inner) if p is not None and p.shape[0]]
+        else:
+            inner = slab[lo:min(hi, D)]
+            want = hi - D if hi > D else 0
+            extra = None if outer is None or want == 0 else outer[:want]
+            parts = [p for p in (inner, extra) if p is not None and p.shape[0]]
+        if not parts:
+            return None, 0
+        if len(parts) == 1:
+            return parts[0], int(parts[0].shape[0])
+        bits = [p.view(torch.int32) if p.dtype == torch.uint32 else p for p in parts]     # torch copies few uint32 tensors
+        both = torch.cat(bits)
+        return (both.view(torch.uint32) if slab.dtype == torch.uint32 else both), int(both.shape[0])
+
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            lo, hb = stack(z0 - halo, z0, below, True)
+            hi, ha = stack(z1, z1 + halo, above, False)
+            d = z1 - z0
+            wb = query('emp_label_dilate_work_bytes' if near else 'emp_label_edt_work_bytes', d, H, W, hb, ha)
+            if wb < 0:
+                raise ValueError(f"{name}: ({hb} + {d} + {ha}) x {H} x {W} voxels exceed the limit of "
+                                 f"{MORPH_MAX_VOXELS} voxels per call, halos included")
+            stats['blocks'] += 1
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            call('emp_' + name, _ptr(slab[z0:z1]), item, d, H, W, _ptr(lo), hb, _ptr(hi), ha, az, ay, ax, limit,
+                 _ptr(work), wb, _ptr(out[z0:z1]), _current_stream(), alg_bytes=d * H * W * (item + out.element_size()))
+    return out
+
+
+def label_edt(slab, sampling=(1, 1, 1), cap=65535, below=None, above=None, block_voxels=None, info=None):
+    """The capped squared Euclidean distance of every labelled voxel to the nearest voxel of another label, background
+    included (emp_label_edt; the definition is in include/emp_hip.h, E5): a (D, H, W) uint16 tensor on the slab's
+    device, 0 on zero voxels and `cap` (1 .. 65535) where no other label lies nearer -- the volume's faces are no
+    candidates.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they are).
+    sampling: the voxel pitch (az, ay, ax), integers in 1 .. 16.  below / above: (h, H, W) stacks of the slab's dtype and
+    device that stand for the slices z = -h .. -1 and z = D .. D + h - 1, None = the volume's face.  A slab of more than
+    block_voxels voxels (None: what one call can take, MORPH_MAX_VOXELS with the halos) is cut into z-blocks of whole
+    slices, each with floor(sqrt(cap - 1)) // az halo slices per side -- views of the slab, continued by below / above at
+    its ends -- so the result is that of the undivided slab.  Every argument error, a CPU tensor among them, is a
+    ValueError before any GPU work; an empty slab gives an empty result.  info: a dict that receives 'blocks' and
+    'work_bytes' (largest workspace of one call)."""
+    return _morph('label_edt', slab, sampling, cap, below, above, block_voxels, info)
+
+
+def label_erode(slab, r2, sampling=(1, 1, 1), below=None, above=None, block_voxels=None, info=None):
+    """The erosion of every label by the ball of squared radius r2 (emp_label_erode; include/emp_hip.h, E5): a new label
+    tensor of the slab's shape and dtype that keeps a voxel's label where its distance to every other label, background
+    included, exceeds r2 and holds 0 elsewhere, so touching objects get a gap; the volume's faces do not erode.  1 <= r2
+    <= 65534 and r2 >= min(sampling)^2.  The other arguments, the blocks (floor(sqrt(r2)) // az halo slices) and the
+    errors are label_edt's."""
+    return _morph('label_erode', slab, sampling, r2, below, above, block_voxels, info)
+
+
+def label_dilate(slab, r2, sampling=(1, 1, 1), below=None, above=None, block_voxels=None, info=None):
+    """The dilation of every label by the ball of squared radius r2 (emp_label_dilate; include/emp_hip.h, E5): a new
+    label tensor of the slab's shape and dtype in which a non-zero voxel keeps its label -- an object never overwrites
+    another -- and a zero voxel takes the label of the nearest labelled voxel within r2, the largest label (unsigned)
+    among equally near ones, or stays 0.  The arguments, the blocks and the errors are label_erode's."""
+    return _morph('label_dilate', slab, sampling, r2, below, above, block_voxels, info)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -299,6 +299,40 @@ def _splitting(finish, connectivity, thing_list, min_size, min_span, group, stat
     return split_finish
 
 
+def _check_morph(morph):
+    """infer_volume's `morph` argument -> None or (op, r2, sampling), before any GPU work"""
+    from ..morphology import check
+    return check(morph)
+
+
+def _morphing(finish, morph, thing_list, shape3d, group, recount, stats):
+    """`finish` with the morphology behind it: every thing class's slab is replaced by morphology.morph_volume's before
+    anything else reads the volumes, and `stats` receives {class: morph_volume's stats}.  recount: an erosion or an
+    opening can take an object's last voxel, so the counts become the distinct labels that remain (the rows of the
+    measured table) -- unless split_objects, which runs next, counts anyway"""
+    if morph is None:
+        return finish
+    from ..measurements import gather_tables
+    from ..morphology import morph_volume
+    op, r2, sampling = morph
+
+    def morph_finish(planes):
+        vols, (z0, z1), counts = finish(planes)
+        counts = dict(counts)
+        for c in vols:
+            if c not in thing_list:
+                continue
+            slab = vols[c] if vols[c].is_contiguous() else vols[c].contiguous()
+            vols[c], stats[c] = morph_volume(slab, shape3d, op, r2, sampling, group=group, z_base=int(z0))
+            if recount and op in ('erode', 'open'):
+                below, above = _neighbour_slices(vols[c], group)
+                table = gather_tables(_hip.measure_labels(vols[c], below=below, above=above, z_base=int(z0)), group)
+                counts[c] = int(table.shape[0])
+        return vols, (z0, z1), counts
+
+    return morph_finish
+
+
 def _check_fill(fill_holes):
     """infer_volume's `fill_holes` argument -> (wanted, cap in voxels or None), before any GPU work"""
     if fill_holes is None:
@@ -404,7 +438,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None, split_objects=None, fill_holes=None):
+                 measure=None, split_objects=None, fill_holes=None, morph=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -470,6 +504,19 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     Datasets, compressed output, pyramid, scores and measurements see the filled labels; stuff classes stay as they
     are and 'instances' do not change.  The result gains 'filled': {class: {'cavities', 'filled', 'voxels_filled',
     'shared', 'too_large'}}, the same on every rank.
+    morph: None = the volumes as they are; (op, r) or (op, r, (az, ay, ax)) = one morphological operation on every thing
+    class's slab on the device (morphology.morph_volume; include/emp_hip.h, E5) BEFORE split_objects and fill_holes, so
+    that an opening cuts a thin bridge and the split then separates and judges the pieces, and a closing's new cavities
+    get filled.  op: 'erode' (a voxel keeps its label where every other label, background included, is farther than
+    r), 'dilate' (a background voxel takes the nearest label within r, the largest among equally near; labelled voxels
+    stay), 'open' (erode, then dilate: every label opened by itself) or 'close' (dilate, then erode, originals kept).
+    r: the radius in the units of the sampling (az, ay, ax), integer voxel pitches in 1 .. 16, (1, 1, 1) by default
+    ((3, 1, 1) for thick sections): exact Euclidean balls, 1 = the 6-neighbourhood, sqrt(2) the 18- and sqrt(3) the
+    26-neighbourhood, up to sqrt(65534).  The volume's faces do not erode.  With several ranks every rank fetches the
+    few slices of its neighbours that the ball reaches.  Datasets, compressed output, pyramid, scores and measurements
+    see the new labels; stuff classes stay as they are.  After 'erode' and 'open', 'instances' become the labels that
+    remain.  The result gains 'morph': {class: {'op', 'r2', 'sampling', 'voxels_removed', 'voxels_added'}}, the same on
+    every rank.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -478,6 +525,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     spacing = _check_measure(measure)
     connectivity = _check_split(split_objects)
     fill_wanted, fill_cap = _check_fill(fill_holes)
+    morph = _check_morph(morph)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -527,12 +575,16 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                                                   bypass, min_size, min_span, group=group)
         return vols, zs, {c: int(cons[c].alive.sum()) for c in labels}
 
+    morphed = {}
+    finish = _morphing(finish, morph, thing_list, shape3d, group, connectivity is None, morphed)
     split = {}
     finish = _splitting(finish, connectivity, thing_list, min_size, min_span, group, split)
     filled = {}
     finish = _filling(finish, fill_wanted, fill_cap, thing_list, shape3d, group, filled)
 
     def done(res):
+        if morph is not None:
+            res['morph'] = morphed
         if connectivity is not None:
             res['split'] = split
         if fill_wanted:

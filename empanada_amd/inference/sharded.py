@@ -165,6 +165,45 @@ def neighbour_slices(slab, group=None):
     return (None if below is None else below.contiguous()), (None if above is None else above.contiguous())
 
 
+def neighbour_slabs(slab, n, group=None):
+    """(below, above) of a rank's (d, H, W) slab: the n slices that lie under its first slice and the n slices over its
+    last one in the volume that the ranks' consecutive slabs make up, as (k, H, W) stacks in z order -- collected from the
+    nearest ranks outward, so a rank that holds fewer than n slices is continued by the next one and an empty rank is
+    skipped; k < n only where the volume ends, and None where nothing lies there (or n == 0).  One gather: every rank
+    gives its first n and its last n slices, or its whole slab where that is no more."""
+    rank, world = _world(group)
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"neighbour_slabs: n must not be negative, got {n}")
+    if world == 1 or n == 0:
+        return None, None
+    bits = slab.view(torch.int32) if slab.dtype == torch.uint32 else slab      # torch copies few uint32 tensors
+    ends = bits if bits.shape[0] <= 2 * n else torch.cat([bits[:n], bits[-n:]])
+    parts = _gather_var(ends.contiguous(), group)
+
+    def collect(ranks, take):
+        got, need = [], n
+        for r in ranks:
+            k = min(need, int(parts[r].shape[0]))
+            if k:
+                got.append(take(parts[r], k))
+                need -= k
+            if need == 0:
+                break
+        return got
+
+    below = collect(range(rank - 1, -1, -1), lambda p, k: p[p.shape[0] - k:])[::-1]
+    above = collect(range(rank + 1, world), lambda p, k: p[:k])
+
+    def joined(got):
+        if not got:
+            return None
+        t = (got[0] if len(got) == 1 else torch.cat(got)).contiguous()
+        return t.view(slab.dtype) if t.dtype != slab.dtype else t
+
+    return joined(below), joined(above)
+
+
 def _all_reduce_sum(a, group=None):
     """int64 numpy vector summed over the ranks"""
     rank, world = _world(group)

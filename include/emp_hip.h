@@ -818,6 +818,53 @@ int emp_label_holes(const void *lab, int item, int64_t D, int64_t H, int64_t W, 
                     int64_t z_base, const int32_t *row_offsets, int64_t n_runs, void *work, int64_t work_bytes,
                     int64_t *out_table, int32_t *n_out, void *stream);
 
+/* ---- E5: label morphology -- exact Euclidean erode and dilate of a label volume, and the distance under both ---------
+ * replaces, on the device, what users of the reference run on a CPU after the fact: scipy.ndimage.binary_erosion /
+ *          binary_dilation / binary_opening / binary_closing or an edt per object (the napari front-end's label tools).
+ * lab is a contiguous (D, H, W) array of item-byte unsigned little-endian integers, item = 1 (uint8) or 4 (uint32; the
+ * bits of an int32 are taken as they are), 0 = background.  Every 32-bit value is a legal label: there is no sentinel.
+ * The sampling (az, ay, ax), integers in 1 .. 16, is the voxel pitch per axis, and the squared distance of two voxels is
+ * d2(v, u) = (az dz)^2 + (ay dy)^2 + (ax dx)^2, an exact integer.
+ *   - Inside distance: for lab[v] != 0, edt(v) = min(cap, min over the voxels u of the volume with lab[u] != lab[v] of
+ *     d2(v, u)) -- background and other objects count alike; positions outside the volume are no candidates (as in
+ *     scipy.ndimage.distance_transform_edt: an object cut by the volume's face is not eroded from that face); without a
+ *     candidate the value is cap.  For lab[v] == 0 the value is 0.  1 <= cap <= 65535, so a uint16 holds every value.
+ *   - Nearest label: for lab[v] == 0, among the voxels u with lab[u] != 0 and d2(v, u) <= r2 the one with the smallest
+ *     d2, among equal d2 the largest label under unsigned comparison (the pooling kernel's tie rule); 0 if there is none.
+ *   - erode:  lab[v] where edt(v) > r2 (computed with cap = r2 + 1), 0 elsewhere: touching objects get a gap.
+ *   - dilate: lab[v] where it is non-zero -- an object never overwrites another -- and the nearest label elsewhere.
+ *   1 <= r2 <= 65534 and r2 >= min(az, ay, ax)^2: below that the ball is a point and the call is refused.
+ * The volume may be continued along z by two halo stacks as E2's neighbour slices are, but of any depth: `below` holds
+ * hb >= 0 slices that stand for z = -hb .. -1 and `above` ha >= 0 slices for z = D .. D + ha - 1; a count of 0 means the
+ * volume's face.  Halo voxels are candidates like any other; the output covers the D slices of lab alone.  With
+ * floor(sqrt(r2)) / az slices on either side (floor(sqrt(cap - 1)) / az for the distance) the result is that of the
+ * undivided volume, so z-blocks and the ranks' slabs need no merge.
+ * Both are computed separably, x then y then z, with w = a_axis^2.  Distance: f = cap on non-zero voxels; in each pass,
+ * for voxel p of label l, best = f[p] and on either side, for k = 1, 2, ... while w k^2 < best: leaving the volume
+ * stops the side; lab[q] != l takes w k^2 and stops the side (that voxel is itself a candidate and all beyond it are
+ * farther); otherwise best = min(best, f[q] + w k^2).  Nearest label: the passes carry the key (d2, label), starting as
+ * (0, lab) on labelled voxels and (r2 + 1, 0) elsewhere, with no stop at labels and k running while w k^2 <= min(best
+ * d2, r2) so that ties are seen.  All arithmetic is integer, there is no atomic and no kernel waits for another, so no
+ * launch shape or z-partition shows in any output.
+ * out is never lab: a pass reads its neighbours' labels.  The intermediates live in `work`, which kernels initialise (no
+ * memset node): two uint16 per voxel of the extended volume for emp_label_edt / emp_label_erode
+ * (emp_label_edt_work_bytes), two uint16 and two uint32 for emp_label_dilate (emp_label_dilate_work_bytes); the queries
+ * return -1 for a shape that a call would refuse.  A call covers at most 2^31 - 1 voxels, halos included: a larger
+ * block is refused with EMP_EINVAL, as is every other argument error, before any launch.  D == 0 is a no-op.
+ * emp_label_edt writes the (D, H, W) uint16 distances, emp_label_erode and emp_label_dilate a (D, H, W) label volume of
+ * the same item size.                                                                                                */
+int64_t emp_label_edt_work_bytes(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha);
+int emp_label_edt(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                  const void *above, int64_t ha, int az, int ay, int ax, int cap, void *work, int64_t work_bytes,
+                  uint16_t *out, void *stream);
+int emp_label_erode(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                    const void *above, int64_t ha, int az, int ay, int ax, int r2, void *work, int64_t work_bytes,
+                    void *out, void *stream);
+int64_t emp_label_dilate_work_bytes(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha);
+int emp_label_dilate(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                     const void *above, int64_t ha, int az, int ay, int ax, int r2, void *work, int64_t work_bytes,
+                     void *out, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
