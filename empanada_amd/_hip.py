@@ -133,6 +133,10 @@ SIGNATURES = {
     'emp_label_erode': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
     'emp_label_dilate_work_bytes': (_L, [_L, _L, _L, _L, _L]),
     'emp_label_dilate': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
+    'emp_label_grow_work_bytes': (_L, [_L, _L, _L]),
+    'emp_label_grow_init': (_I, [_P, _I, _P, _L, _L, _L, _P, _P, _L, _P]),
+    'emp_label_grow_sweep': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
+    'emp_label_grow_paint': (_I, [_P, _P, _I, _L, _P, _L, _I, _P, _I, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -1302,6 +1306,259 @@ def label_dilate(slab, r2, sampling=(1, 1, 1), below=None, above=None, block_vox
     another -- and a zero voxel takes the label of the nearest labelled voxel within r2, the largest label (unsigned)
     among equally near ones, or stays 0.  The arguments, the blocks and the errors are label_erode's."""
     return _morph('label_dilate', slab, sampling, r2, below, above, block_voxels, info)
+
+
+GROW_MAX_VOXELS = MEASURE_MAX_VOXELS         # voxels per emp_label_grow_* call
+GROW_SWEEPS_PER_SYNC = 4                     # sweeps launched between two reads of the counters
+_GROW_SLOTS = 8
+
+
+def _grow_operand(what, t, dtypes, shape=None, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"label_grow: {what} must be a tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise ValueError(f"label_grow: {what} has dtype {t.dtype}, expected one of {dtypes}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"label_grow: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"label_grow: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if not t.is_cuda:
+        raise ValueError(f"label_grow: {what} is on {t.device}, expected the GPU")
+    if device is not None and t.device != device:
+        raise ValueError(f"label_grow: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+def _grow_bound(what, value, lo, hi):
+    import numbers
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
+        raise ValueError(f"label_grow: {what} must be an integer in {lo} .. {hi}, got {value!r}")
+    return int(value)
+
+
+class LabelGrow:
+    """What _hip.label_grow returns: `state`, the (D, H, W) int64 tensor of the keys dist << 32 | ~owner (include/emp_hip.h,
+    E6; all-ones, -1, = not reached), `sweeps`, owners(), paint(), and for a slab that is one part of a larger volume
+    ends() and resume().  It keeps the slab, the state and the tile lists of the slab's z-blocks on the device."""
+
+    def __init__(self, slab, max_sweeps, stats):
+        self.slab, self._max_sweeps, self._stats = slab, max_sweeps, stats
+        self.state = torch.empty(tuple(slab.shape), dtype=torch.int64, device=slab.device)
+        self._blocks, self._seed_top = [], 0
+
+    @property
+    def sweeps(self):
+        return self._stats['sweeps']
+
+    def _halo(self, what, pair):
+        if pair is None:
+            return None
+        H, W = int(self.slab.shape[1]), int(self.slab.shape[2])
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError(f"label_grow: {what} must be None or (labels, state): one (H, W) slice of each")
+        return (_grow_operand(f"{what}'s labels", pair[0], (self.slab.dtype,), (H, W), self.slab.device),
+                _grow_operand(f"{what}'s state", pair[1], (torch.int64,), (H, W), self.slab.device))
+
+    def ends(self):
+        """((labels, state) of the first slice, (labels, state) of the last one): what the slab's neighbours take as
+        their `above` and `below`; views, so copy what has to outlive the next resume().  None for an empty slab."""
+        if self.slab.shape[0] == 0:
+            return None
+        return (self.slab[0], self.state[0]), (self.slab[-1], self.state[-1])
+
+    def resume(self, below=None, above=None):
+        """Sweep on from the state as it is, with `below` / `above` -- each None (the volume's face) or (labels, state),
+        one (H, W) slice of the neighbouring slab each -- until nothing changes in this slab; returns whether any key
+        fell.  Rounds over the slab's z-blocks until a whole round changes nothing; each block sweeps until a sweep
+        stores nothing, GROW_SWEEPS_PER_SYNC sweeps between two reads of the counters.  More than max_sweeps sweeps in
+        all is a RuntimeError."""
+        below, above = self._halo("below", below), self._halo("above", above)
+        slab, state, stats = self.slab, self.state, self._stats
+        D, H, W = (int(s) for s in slab.shape)
+        if slab.numel() == 0:
+            return False
+        item = slab.element_size()
+        fell = False
+        with torch.cuda.device(slab.device):
+            while True:
+                stats['rounds'] += 1
+                round_fell = False
+                for b in self._blocks:
+                    z0, z1 = b['z0'], b['z1']
+                    lo = below if z0 == 0 else (slab[z0 - 1], state[z0 - 1])
+                    hi = above if z1 == D else (slab[z1], state[z1])
+                    force = (1 if lo is not None else 0) | (2 if hi is not None else 0)
+                    if b['listed'] == 0:
+                        continue
+                    settled = False
+                    while not settled:
+                        batch = []
+                        for _ in range(GROW_SWEEPS_PER_SYNC):
+                            if stats['sweeps'] >= self._max_sweeps:
+                                break
+                            slot = b['turns'] % _GROW_SLOTS
+                            call('emp_label_grow_sweep', _ptr(slab[z0:z1]), item, z1 - z0, H, W, _ptr(state[z0:z1]),
+                                 _ptr(lo[0]) if lo else None, _ptr(lo[1]) if lo else None,
+                                 _ptr(hi[0]) if hi else None, _ptr(hi[1]) if hi else None, _ptr(b['work']),
+                                 b['work'].numel(), b['listed'], b['turns'] & 1, force, slot, _current_stream())
+                            b['turns'] += 1
+                            stats['sweeps'] += 1
+                            force = 0
+                            batch.append(slot)
+                        seen = b['work'][:8 * (1 + _GROW_SLOTS)].view(torch.int64).cpu().tolist()[1:]
+                        for slot in batch:
+                            if seen[slot] == b['seen'][slot]:
+                                settled = True                # a sweep that stored nothing: those after it did not either
+                                break
+                            stats['sweeps_needed'] += 1
+                            round_fell = True
+                            b['seen'][slot] = seen[slot]
+                        stats['sweeps_needed'] += 1 if settled else 0
+                        if not settled and stats['sweeps'] >= self._max_sweeps:
+                            raise RuntimeError(f"label_grow: not settled after max_sweeps = {self._max_sweeps} sweeps")
+                fell = fell or round_fell
+                if not round_fell or len(self._blocks) == 1:
+                    return fell
+
+    def owners(self):
+        """the owner of every voxel as a (D, H, W) uint32 tensor, 0 = no seed reaches it or background"""
+        out = torch.empty(tuple(self.slab.shape), dtype=torch.uint32, device=self.slab.device)
+        if out.numel():
+            with torch.cuda.device(self.slab.device):
+                for b in self._blocks:
+                    z0, z1 = b['z0'], b['z1']
+                    call('emp_label_grow_paint', _ptr(self.state[z0:z1]), None, self.slab.element_size(),
+                         self.state[z0:z1].numel(), None, 0, 1, _ptr(out[z0:z1]), 4, _current_stream())
+        return out
+
+    def paint(self, lut, out=None, dtype=None):
+        """out(v) = lut[owner(v)] where a seed owns v, the slab's label elsewhere.  lut: one value per seed id, entry 0
+        unused (a tensor on the slab's device or anything numpy converts), so it must be longer than the largest seed
+        id.  out=None: a fresh (D, H, W) tensor of `dtype` (None: the slab's); out=the slab itself: in place, only the
+        voxels whose value changes are written; any other `out` is a contiguous (D, H, W) uint8 or int32 / uint32 tensor
+        on the slab's device that overlaps neither the slab nor the state.  A value that the output's item size cannot
+        hold is a ValueError before anything is written, and so is every other argument error."""
+        import numpy as np
+        slab = self.slab
+        dev = slab.device
+        if isinstance(lut, torch.Tensor):
+            if lut.dtype not in (torch.uint32, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"paint: lut has dtype {lut.dtype}, expected an integer tensor")
+            lut_dev = lut.to(dev)
+            wide = lut_dev.view(torch.int32).long() & 0xffffffff if lut_dev.dtype == torch.uint32 else lut_dev.long()
+        else:
+            arr = np.asarray(lut)
+            if arr.dtype.kind not in 'iu':
+                raise ValueError(f"paint: lut has dtype {arr.dtype}, expected integers")
+            wide = torch.from_numpy(arr.astype(np.int64).reshape(-1)).to(dev)
+        if wide.dim() != 1:
+            raise ValueError(f"paint: lut has shape {tuple(wide.shape)}, expected one dimension")
+        if wide.numel() <= self._seed_top:
+            raise ValueError(f"paint: lut has {wide.numel()} entries, the largest seed id is {self._seed_top}")
+        if out is None:
+            odt = slab.dtype if dtype is None else dtype
+            if odt not in (torch.uint8, torch.int32, torch.uint32):
+                raise ValueError(f"paint: dtype must be torch.uint8, int32 or uint32, got {odt}")
+        else:
+            if dtype is not None and dtype != out.dtype:
+                raise ValueError(f"paint: dtype={dtype} given together with an out of {out.dtype}")
+            _grow_operand("out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), dev)
+            odt = out.dtype
+        item = 1 if odt == torch.uint8 else 4
+        same = out is not None and out.data_ptr() == slab.data_ptr() and item == slab.element_size()
+        if out is not None and slab.numel():
+            b0, b1 = out.data_ptr(), out.data_ptr() + out.numel() * item
+            for what, t in (("slab", slab), ("state", self.state)):
+                a0 = t.data_ptr()
+                if not (same and t is slab) and a0 < b1 and b0 < a0 + t.numel() * t.element_size():
+                    raise ValueError(f"paint: out overlaps the {what}" + (" without being the slab itself" if t is slab else ""))
+        top = 255 if item == 1 else 0xffffffff
+        if wide.numel() > 1 and (int(wide[1:].min()) < 0 or int(wide[1:].max()) > top):
+            raise ValueError(f"paint: the lut holds values outside 0 .. {top}, which a {item}-byte output cannot hold")
+        if item == 1 and slab.element_size() == 4 and slab.numel():
+            bits = slab.view(torch.int32)
+            if int(bits.min()) < 0 or int(bits.max()) > 255:
+                raise ValueError("paint: the slab holds labels above 255, which a 1-byte output cannot hold")
+        if out is None:
+            out = torch.empty(tuple(slab.shape), dtype=odt, device=dev)
+        if slab.numel() == 0:
+            return out
+        lut32 = _low32(wide).contiguous()
+        with torch.cuda.device(dev):
+            for b in self._blocks:
+                z0, z1 = b['z0'], b['z1']
+                call('emp_label_grow_paint', _ptr(self.state[z0:z1]), _ptr(slab[z0:z1]), slab.element_size(),
+                     self.state[z0:z1].numel(), _ptr(lut32), lut32.numel(), 0, _ptr(out[z0:z1]), item, _current_stream(),
+                     alg_bytes=self.state[z0:z1].numel() * (8 + slab.element_size() + item))
+        return out
+
+
+def label_grow(slab, seeds, below=None, above=None, block_voxels=None, max_sweeps=None, info=None):
+    """Geodesic growth of seeds inside the objects of a label slab (emp_label_grow_*; the definition is in
+    include/emp_hip.h, E6): every labelled voxel goes to the seed that reaches it first along 6-connected paths inside
+    the voxel's own label, the largest seed id (unsigned) among equally near ones.  Returns a LabelGrow: owners() is the
+    (D, H, W) uint32 owner volume, paint(lut) writes a value per seed id over the voxels it owns, `sweeps` the sweeps
+    launched.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they are); seeds:
+    uint32 (or int32) of the same shape and device, 0 = no seed; a seed on a zero voxel is ignored.  below / above: None
+    (the volume's face) or (labels, state), ONE (H, W) slice each of the neighbouring slab's labels and of its
+    LabelGrow.state; LabelGrow.resume() sweeps on with new ones.  A slab of more than block_voxels voxels (None:
+    GROW_MAX_VOXELS, the kernel's limit) is cut into z-blocks of whole slices; each reads its neighbours' end slices of
+    state, and rounds over all blocks go on until a whole round changes nothing, so the result is the undivided slab's.
+    Each block sweeps until a sweep stores nothing; the counters are read every GROW_SWEEPS_PER_SYNC = 4 sweeps (one host
+    sync) and once after the initialisation.  max_sweeps bounds the sweeps of the call and of every resume() together
+    (None: (voxels + 2) x blocks -- no path is longer than the labelled voxels); reaching it unsettled is a
+    RuntimeError.  Every argument error is a ValueError before any GPU work.  info: a dict that receives 'blocks',
+    'sweeps' (launched), 'sweeps_needed' (per visit of a block, up to and including the first that stored nothing),
+    'rounds', 'active_tiles' (listed tiles: those that hold a labelled voxel) and 'work_bytes' (state included); it
+    keeps counting through resume()."""
+    slab = _grow_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+    if slab.dim() != 3:
+        raise ValueError(f"label_grow: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    seeds = _grow_operand("seeds", seeds, (torch.uint32, torch.int32), (D, H, W), dev)
+    if block_voxels is None:
+        block_voxels = GROW_MAX_VOXELS
+    else:
+        block_voxels = _grow_bound("block_voxels", block_voxels, 1, GROW_MAX_VOXELS)
+    if max_sweeps is not None:
+        max_sweeps = _grow_bound("max_sweeps", max_sweeps, 1, 2 ** 62)
+    if H * W > block_voxels:
+        raise ValueError(f"label_grow: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = max(1, block_voxels // max(H * W, 1))
+    n_blocks = -(-D // per)
+    stats = {} if info is None else info
+    stats.update(blocks=n_blocks, sweeps=0, sweeps_needed=0, rounds=0, active_tiles=0, work_bytes=0)
+    if below is not None or above is not None:                    # checked before the state is allocated
+        probe = LabelGrow.__new__(LabelGrow)
+        probe.slab = slab
+        probe._halo("below", below), probe._halo("above", above)
+    if slab.numel():
+        require_gpu()
+    g = LabelGrow(slab, (slab.numel() + 2) * max(n_blocks, 1) if max_sweeps is None else max_sweeps, stats)
+    if slab.numel() == 0:
+        return g
+    item = slab.element_size()
+    with torch.cuda.device(dev):
+        stats['work_bytes'] = g.state.numel() * 8
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            wb = query('emp_label_grow_work_bytes', z1 - z0, H, W)
+            if wb < 0:
+                raise ValueError(f"label_grow: {z1 - z0} x {H} x {W} voxels exceed the limit of {GROW_MAX_VOXELS} per call")
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            stats['work_bytes'] += int(wb)
+            call('emp_label_grow_init', _ptr(slab[z0:z1]), item, _ptr(seeds[z0:z1]), z1 - z0, H, W, _ptr(g.state[z0:z1]),
+                 _ptr(work), wb, _current_stream(), alg_bytes=(z1 - z0) * H * W * (item + 12))
+            g._blocks.append(dict(z0=z0, z1=z1, work=work, turns=0, seen=[0] * _GROW_SLOTS, listed=0))
+        for b in g._blocks:                                       # one sync: the lengths of the lists
+            b['listed'] = int(b['work'][:8].view(torch.int64).item())
+            stats['active_tiles'] += b['listed']
+        s32 = seeds.view(torch.int32)
+        g._seed_top = 2 ** 32 - 1 if int(s32.min()) < 0 else int(s32.max())
+    g.resume(below, above)
+    return g
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -10,7 +10,7 @@ module works on O(#components) tables: joining the components of z-blocks and of
 import numpy as np
 import torch
 
-__all__ = ['COLUMNS', 'merge_blocks', 'seam_pairs', 'plan', 'split_volume']
+__all__ = ['COLUMNS', 'merge_blocks', 'seam_pairs', 'plan', 'merged_table', 'split_volume']
 
 COLUMNS = ('label', 'voxels', 'first', 'z0', 'y0', 'x0', 'z1', 'y1', 'x1')
 _SHIFTS = {6: [(0, 0)],
@@ -154,6 +154,39 @@ def plan(table, min_size=None, min_span=None):
     return lut, stats
 
 
+def merged_table(lc, connectivity, group=None, who="merged_table"):
+    """The component table of the volume whose consecutive z-slabs the ranks of `group` hold, from every rank's own
+    _hip.label_components result `lc`: (table, mine).  The ranks gather their tables and exchange their end slices --
+    labels and provisional ids, as the measurements exchange theirs (sharded.neighbour_slices) -- each finds the pairs
+    that touch across the seam below it, and every rank computes the same merged table; mine[k] is the row of this
+    rank's component k in it.  A single rank: (lc.table, None)."""
+    from .inference import sharded
+    rank, world = sharded._world(group)
+    if world == 1:
+        return lc.table, None
+    slab = lc.slab
+    dev = slab.device
+    tables = sharded._gather_var(lc.table, group)
+    base = sum(int(t.shape[0]) for t in tables[:rank])
+    if sum(int(t.shape[0]) for t in tables) > _MAX_LABEL:
+        raise ValueError(f"{who}: the ranks' provisional components do not fit 32-bit ids")
+    H, W = int(slab.shape[1]), int(slab.shape[2])
+    ends = torch.zeros((2 if slab.shape[0] else 0, H, W), dtype=torch.uint32, device=dev)
+    if slab.shape[0] and lc.n:
+        ids = base + 1 + torch.arange(lc.n, dtype=torch.int64, device=dev)
+        ends = torch.stack([lc.paint_slice(ids, z).view(torch.int32) for z in (0, int(slab.shape[0]) - 1)])
+        ends = ends.view(torch.uint32)
+    below_lab, _ = sharded.neighbour_slices(slab, group)
+    below_ids, _ = sharded.neighbour_slices(ends, group)
+    if below_lab is not None and slab.shape[0]:
+        seam = seam_pairs(below_lab, below_ids, slab[0], ends[0], connectivity)
+    else:
+        seam = torch.zeros((0, 2), dtype=torch.int64, device=dev)
+    seams = sharded._gather_var(seam.contiguous(), group)
+    table, index = merge_blocks(tables, seams, return_index=True)
+    return table, index[base:base + lc.n]
+
+
 def split_volume(slab, connectivity=26, min_size=None, min_span=None, group=None, z_base=0, out=None):
     """The repair of one class: every label of `slab` -- a rank's (d, H, W) device slab of a volume whose slices
     [z_base, z_base + d) it holds, uint8 or int32 / uint32 -- is split into its connected components and `plan` decides
@@ -164,33 +197,10 @@ def split_volume(slab, connectivity=26, min_size=None, min_span=None, group=None
     (sharded.neighbour_slices) -- each finds the pairs that touch across the seam below it, and every rank computes the
     same merged table and the same plan and paints its own slab.  A rank without slices takes part with an empty slab."""
     from . import _hip
-    from .inference import sharded
     connectivity = _check_connectivity(connectivity)
-    rank, world = sharded._world(group)
     lc = _hip.label_components(slab, connectivity, z_base=z_base)
     dev = slab.device
-    if world == 1:
-        table, mine = lc.table, None
-    else:
-        tables = sharded._gather_var(lc.table, group)
-        base = sum(int(t.shape[0]) for t in tables[:rank])
-        if sum(int(t.shape[0]) for t in tables) > _MAX_LABEL:
-            raise ValueError("split_volume: the ranks' provisional components do not fit 32-bit ids")
-        H, W = int(slab.shape[1]), int(slab.shape[2])
-        ends = torch.zeros((2 if slab.shape[0] else 0, H, W), dtype=torch.uint32, device=dev)
-        if slab.shape[0] and lc.n:
-            ids = base + 1 + torch.arange(lc.n, dtype=torch.int64, device=dev)
-            ends = torch.stack([lc.paint_slice(ids, z).view(torch.int32) for z in (0, int(slab.shape[0]) - 1)])
-            ends = ends.view(torch.uint32)
-        below_lab, _ = sharded.neighbour_slices(slab, group)
-        below_ids, _ = sharded.neighbour_slices(ends, group)
-        if below_lab is not None and slab.shape[0]:
-            seam = seam_pairs(below_lab, below_ids, slab[0], ends[0], connectivity)
-        else:
-            seam = torch.zeros((0, 2), dtype=torch.int64, device=dev)
-        seams = sharded._gather_var(seam.contiguous(), group)
-        table, index = merge_blocks(tables, seams, return_index=True)
-        mine = index[base:base + lc.n]
+    table, mine = merged_table(lc, connectivity, group, "split_volume")
     lut, stats = plan(table, min_size, min_span)
     lut = torch.from_numpy(lut.astype(np.int64)).to(dev)
     if mine is not None:

@@ -333,6 +333,38 @@ def _morphing(finish, morph, thing_list, shape3d, group, recount, stats):
     return morph_finish
 
 
+def _check_separate(separate):
+    """infer_volume's `separate` argument -> None or (r2, min_core, sampling), before any GPU work"""
+    from ..separation import check
+    return check(separate)
+
+
+def _separating(finish, separate, thing_list, shape3d, group, recount, stats):
+    """`finish` with the separation behind it: every thing class's slab goes through separation.separate_volume in
+    place, after the morphology and before anything else reads the volumes, and `stats` receives {class:
+    separate_volume's stats}.  recount: every piece that got a new label is one object more, so the counts grow by
+    'pieces_added' -- unless split_objects, which runs next, counts anyway"""
+    if separate is None:
+        return finish
+    from ..separation import separate_volume
+    r2, min_core, sampling = separate
+
+    def separate_finish(planes):
+        vols, (z0, z1), counts = finish(planes)
+        counts = dict(counts)
+        for c in vols:
+            if c not in thing_list:
+                continue
+            if not vols[c].is_contiguous():
+                vols[c] = vols[c].contiguous()
+            _, stats[c] = separate_volume(vols[c], shape3d, r2, min_core, sampling, group=group, z_base=int(z0))
+            if recount:
+                counts[c] = int(counts[c]) + stats[c]['pieces_added']
+        return vols, (z0, z1), counts
+
+    return separate_finish
+
+
 def _check_fill(fill_holes):
     """infer_volume's `fill_holes` argument -> (wanted, cap in voxels or None), before any GPU work"""
     if fill_holes is None:
@@ -438,7 +470,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None, split_objects=None, fill_holes=None, morph=None):
+                 measure=None, split_objects=None, fill_holes=None, morph=None, separate=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -517,6 +549,19 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     see the new labels; stuff classes stay as they are.  After 'erode' and 'open', 'instances' become the labels that
     remain.  The result gains 'morph': {class: {'op', 'r2', 'sampling', 'voxels_removed', 'voxels_added'}}, the same on
     every rank.
+    separate: None = the volumes as they are, where two objects that touch carry one id; r, (r, min_core) or (r, min_core,
+    (az, ay, ax)) = every thing class's slab goes through separation.separate_volume on the device (include/emp_hip.h,
+    E6) AFTER morph and BEFORE split_objects and fill_holes: every label is eroded by the exact Euclidean ball of radius
+    r (read as morph reads it, in the units of the sampling), the cores that remain are labelled, and a label with two
+    or more cores of at least min_core voxels (default 1) is divided among them -- every voxel goes to the core that
+    reaches it first along 6-connected paths inside the object, the later-numbered core among equally near ones.  The
+    largest piece keeps the id and every further piece gets a new id above the class's largest; no surface moves, no
+    voxel is lost or added, and every other label stays exactly as it is.  A voxel of a divided object that no core
+    reaches keeps the id; split_objects, which runs next, judges such crumbs and every new piece by min_size /
+    min_span.  With several ranks every rank exchanges one end slice of the growth's state per side and round.
+    Datasets, compressed output, pyramid, scores and measurements see the new labels; stuff classes stay as they are.
+    'instances' grow by the pieces added and the result gains 'separated': {class: {'r2', 'min_core', 'sampling',
+    'objects_in', 'objects_separated', 'pieces_added', 'voxels_moved', 'sweeps'}}, the same on every rank.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -526,6 +571,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     connectivity = _check_split(split_objects)
     fill_wanted, fill_cap = _check_fill(fill_holes)
     morph = _check_morph(morph)
+    separate = _check_separate(separate)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -577,6 +623,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
 
     morphed = {}
     finish = _morphing(finish, morph, thing_list, shape3d, group, connectivity is None, morphed)
+    separated = {}
+    finish = _separating(finish, separate, thing_list, shape3d, group, connectivity is None, separated)
     split = {}
     finish = _splitting(finish, connectivity, thing_list, min_size, min_span, group, split)
     filled = {}
@@ -585,6 +633,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     def done(res):
         if morph is not None:
             res['morph'] = morphed
+        if separate is not None:
+            res['separated'] = separated
         if connectivity is not None:
             res['split'] = split
         if fill_wanted:

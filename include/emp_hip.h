@@ -865,6 +865,63 @@ int emp_label_dilate(const void *lab, int item, int64_t D, int64_t H, int64_t W,
                      const void *above, int64_t ha, int az, int ay, int ax, int r2, void *work, int64_t work_bytes,
                      void *out, void *stream);
 
+/* ---- E6: geodesic growth -- seeds regrown inside the objects of a label volume -----------------------------------------
+ * replaces, on the device, the flood that users of the reference run on a CPU to separate touching objects: erode, label
+ *          the cores, grow them back inside the object (a watershed on a binary mask).
+ * Inputs.  L: a label volume (D, H, W), item = 1 (uint8) or 4 (uint32; the bits of an int32 are taken as they are); every
+ * 32-bit value other than 0 is a label.  S: a seed volume, uint32, of the same shape; a seed on a voxel with L = 0 is
+ * ignored.
+ * Geodesic distance.  For a voxel v with L(v) = l != 0, g(v) is the number of steps of the shortest 6-connected path
+ * from v to a seed voxel, where EVERY voxel of the path carries the label l.  If no such path exists, g(v) = infinity.
+ * Seeds have g = 0.  The distance is a 32-bit count and has no cap.
+ * Owner.   g(v) = 0:               owner(v) = S(v)
+ *          g(v) = k >= 1, finite:  the largest owner(u), compared unsigned, over the face neighbours u of v with
+ *                                  L(u) = l and g(u) = k - 1
+ *          g(v) = infinity or L(v) = 0:  owner(v) = 0
+ *   - The tie rule is the one the pooling and dilation kernels use.
+ *   - Induction over k makes the owner unique.
+ *   - Growth never crosses from one label into another and never enters background.
+ *   - Positions outside the volume are no neighbours.
+ * Equivalent fixed point.  It is what makes a parallel schedule legal.
+ *   - Keep one key per voxel: dist << 32 | ~owner.
+ *   - Seeds are fixed at 0 << 32 | ~S.
+ *   - Every other labelled voxel repeatedly takes min over same-label face neighbours of (key(u) + (1 << 32)).
+ *   - All-ones means "not reached" (and stays all-ones under the addition).
+ *   - Started from all-ones, the keys only fall.
+ *   - The unique fixed point is the definition above, in whatever order voxels are updated.
+ * Relation to the reference.  Its inference/watershed.py:mask_watershed is a FIFO flood from the markers with
+ * connectivity 1.  It computes the same distances and differs only in who wins a tie: there the first in queue order,
+ * here the largest owner.  No BC engine is part of this.
+ * `state` is the (D, H, W) array of those keys, one aligned uint64 per voxel, owned by the caller: it is the interface
+ * between sweeps, z-blocks and ranks.  `work` (emp_label_grow_work_bytes; -1 for a shape that a call would refuse) holds
+ * the list of tiles (8 x 8 x 64 voxels) that hold a labelled voxel, two byte arrays of the tiles that are due, and the
+ * counters; kernels initialise all of it.  A call covers at most 2^31 - 1 voxels: a larger one is refused with
+ * EMP_EINVAL, as is every other argument error, before any launch.  D == 0 is a no-op.
+ * emp_label_grow_init   writes every key (seeds 0 << 32 | ~S, all else all-ones), the list, and marks as due the tiles
+ *                       that hold a seed or face one.  work + 0 then holds the uint64 length of the list.
+ * emp_label_grow_sweep  one workgroup per listed tile (n_listed = that length); a tile that is not due is left at once.
+ *                       The others load the tile and a one-voxel ring of labels and keys into LDS, relax there until
+ *                       nothing in the tile changes, write the lowered keys back and mark the tiles behind the faces
+ *                       on which a key fell as due for the next sweep.  The ring reads the keys as they are at that
+ *                       moment.  below / above: ONE slice each of (labels, state) of the neighbouring z-block or rank,
+ *                       both null = the volume's face; force bit 0 / 1 runs the tiles on the first / last slice
+ *                       whatever their marks say (the halo has changed).  turn: 0 for the first sweep after the
+ *                       initialisation, then alternating -- which of the two mark arrays is read.  A block that stored
+ *                       anything adds one to the uint64 at work + 8 (1 + slot), slot in 0 .. 7: a sweep after which
+ *                       its counter has not moved has reached the fixed point of what it could see.
+ * emp_label_grow_paint  over n voxels: mode 0, dst = owner ? lut[owner] : L (lut: n_lut uint32, entry 0 unused; an owner
+ *                       >= n_lut keeps L), in place on the labels -- only voxels whose value changes are written -- or
+ *                       into another array of item size 1 or 4 that does not overlap them; mode 1, dst = owner, uint32. */
+int64_t emp_label_grow_work_bytes(int64_t D, int64_t H, int64_t W);
+int emp_label_grow_init(const void *lab, int item, const uint32_t *seeds, int64_t D, int64_t H, int64_t W,
+                        uint64_t *state, void *work, int64_t work_bytes, void *stream);
+int emp_label_grow_sweep(const void *lab, int item, int64_t D, int64_t H, int64_t W, uint64_t *state,
+                         const void *below_lab, const uint64_t *below_state, const void *above_lab,
+                         const uint64_t *above_state, void *work, int64_t work_bytes, int64_t n_listed, int turn,
+                         int force, int slot, void *stream);
+int emp_label_grow_paint(const uint64_t *state, const void *lab, int item, int64_t n, const uint32_t *lut,
+                         int64_t n_lut, int mode, void *dst, int dst_item, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
