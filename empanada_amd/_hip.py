@@ -137,6 +137,13 @@ SIGNATURES = {
     'emp_label_grow_init': (_I, [_P, _I, _P, _L, _L, _L, _P, _P, _L, _P]),
     'emp_label_grow_sweep': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
     'emp_label_grow_paint': (_I, [_P, _P, _I, _L, _P, _L, _I, _P, _I, _P]),
+    'emp_label_mesh_count_work_bytes': (_L, [_L]),
+    'emp_label_mesh_count': (_I, [_P, _I, _L, _L, _L, _P, _P, _I, _P, _L, _P, _P]),
+    'emp_label_mesh_emit': (_I, [_P, _I, _L, _L, _L, _P, _P, _I, _L, _P, _L, _L, _P, _P, _P, _P]),
+    'emp_label_mesh_index_work_bytes': (_L, [_L]),
+    'emp_label_mesh_index': (_I, [_P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P]),
+    'emp_mesh_neighbours': (_I, [_P, _L, _P, _L, _P, _P]),
+    'emp_mesh_smooth': (_I, [_P, _P, _L, _F, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
     'emp_track_lift': (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     'emp_track_lift_yz': (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P]),
@@ -1559,6 +1566,211 @@ def label_grow(slab, seeds, below=None, above=None, block_voxels=None, max_sweep
         g._seed_top = 2 ** 32 - 1 if int(s32.min()) < 0 else int(s32.max())
     g.resume(below, above)
     return g
+
+
+MESH_MAX_VOXELS = 2 ** 26           # voxels per emp_label_mesh_count / _emit call: 14 items per voxel fit the int32 scan
+MESH_MAX_CORNERS = 2 ** 32          # corners of the whole volume: the key holds the corner number in 32 bits
+MESH_MAX_ITEMS = 2 ** 31 - 1        # vertices, and quads, of one mesh: int32 indices
+MESH_OBJECT_COLUMNS = 5
+
+
+def _mesh_operand(name, what, t, dtype=None, shape=None, device=None):
+    try:
+        _expect(f"{name}: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+def _mesh_int(name, what, value, lo):
+    import numbers
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo:
+        raise ValueError(f"{name}: {what} must be an integer >= {lo}, got {value!r}")
+    return int(value)
+
+
+def label_mesh(slab, below=None, above=None, z_base=0, depth=None, top=True, block_voxels=None, info=None):
+    """The unsorted vertex keys and quad records of a label slab (emp_label_mesh_count / _emit; the definition is in
+    include/emp_hip.h, E7): (keys, (qkeys, qdirs)) on the slab's device -- keys (nv,) int64, the bits of label << 32 |
+    corner for every vertex on a corner plane the slab owns; qkeys (nq,) int64, label << 32 | lowest corner of the quad,
+    and qdirs (nq,) int32, its direction code (-z 0, +z 1, -y 2, +y 3, -x 4, +x 5), in (z, y, x, direction) order of the
+    owning voxel.  mesh_finish turns them, or the concatenation in z order of those of several slabs, into the mesh.
+    slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they are).  below / above:
+    (H, W) tensors of the slab's dtype and device that stand for the slices at z = -1 and z = D, None = background.
+    z_base: the slab's first slice in the volume; depth: the volume's depth (None: z_base + D), which fixes nothing but
+    the limit (depth + 1) (H + 1) (W + 1) <= 2^32 -- a ValueError otherwise.  top: the slab is the volume's last one and
+    owns corner plane D as well; a slab that is not leaves that plane to the slab above it.  A slab of more than
+    block_voxels voxels (None: MESH_MAX_VOXELS, the kernels' limit) is cut into z-blocks of whole slices with their true
+    neighbour slices; a single slice above the limit is a ValueError.  An empty or all-zero slab gives zero-row outputs.
+    One host sync per block (the two totals).  info: a dict that receives 'blocks' (kernel calls made), 'vertices',
+    'quads' and 'work_bytes' (largest workspace of one call)."""
+    name = "label_mesh"
+    slab = _mesh_operand(name, "slab", slab)
+    if slab.dim() != 3:
+        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if below is not None:
+        below = _mesh_operand(name, "below", below, slab.dtype, (H, W), dev)
+    if above is not None:
+        above = _mesh_operand(name, "above", above, slab.dtype, (H, W), dev)
+    z_base = _mesh_int(name, "z_base", z_base, 0)
+    depth = z_base + D if depth is None else _mesh_int(name, "depth", depth, z_base + D)
+    if not isinstance(top, (bool,)):
+        raise ValueError(f"{name}: top must be True or False, got {top!r}")
+    if block_voxels is None:
+        block_voxels = MESH_MAX_VOXELS
+    elif _mesh_int(name, "block_voxels", block_voxels, 1) > MESH_MAX_VOXELS:
+        raise ValueError(f"{name}: block_voxels must lie in 1 .. {MESH_MAX_VOXELS}, got {block_voxels!r}")
+    stats = {} if info is None else info
+    stats.update(blocks=0, vertices=0, quads=0, work_bytes=0)
+    empty = (torch.zeros((0,), dtype=torch.int64, device=dev),
+             (torch.zeros((0,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev)))
+    if slab.numel() == 0:
+        return empty
+    if (depth + 1) * (H + 1) * (W + 1) > MESH_MAX_CORNERS:
+        raise ValueError(f"{name}: a volume of {depth} x {H} x {W} voxels has {(depth + 1) * (H + 1) * (W + 1)} corners, "
+                         f"above the limit of 2^32 = {MESH_MAX_CORNERS} that the 32-bit corner number of a key sets")
+    if H * W > block_voxels:
+        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    require_gpu()
+    item = slab.element_size()
+    per = max(1, int(block_voxels) // (H * W))
+    keys, qkeys, qdirs = [], [], []
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            part = slab[z0:z1]
+            lo = below if z0 == 0 else slab[z0 - 1]
+            hi = above if z1 == D else slab[z1]
+            d = z1 - z0
+            last = 1 if (top and z1 == D) else 0
+            rows = d * H + (d + last) * (H + 1)
+            wb = query('emp_label_mesh_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_mesh_count', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), last, _ptr(work), wb, _ptr(offs),
+                 _current_stream(), alg_bytes=d * H * W * item)
+            nq, total = (int(v) for v in offs[[d * H, rows]].tolist())
+            nv = total - nq
+            stats['blocks'] += 1
+            stats['vertices'] += nv
+            stats['quads'] += nq
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb) + 4 * (rows + 1))
+            if nv == 0 and nq == 0:
+                continue
+            vk = torch.empty((nv,), dtype=torch.int64, device=dev)
+            qk = torch.empty((nq,), dtype=torch.int64, device=dev)
+            qd = torch.empty((nq,), dtype=torch.int32, device=dev)
+            call('emp_label_mesh_emit', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), last, z_base + z0, _ptr(offs), nq,
+                 nv, _ptr(vk), _ptr(qk), _ptr(qd), _current_stream(), alg_bytes=d * H * W * item + 8 * nv + 12 * nq)
+            keys.append(vk)
+            qkeys.append(qk)
+            qdirs.append(qd)
+    if not keys:
+        return empty
+    if len(keys) == 1:
+        return keys[0], (qkeys[0], qdirs[0])
+    return torch.cat(keys), (torch.cat(qkeys), torch.cat(qdirs))
+
+
+def mesh_finish(keys, quads, shape, info=None):
+    """(vertices, quads, objects) of E7 from label_mesh's (keys, (qkeys, qdirs)) of a whole volume -- of one slab, or
+    of several concatenated in z order: the keys are sorted over all 64 bits and the quads stably over the label bits
+    (sort_u64_i32), then emp_label_mesh_index cuts the objects, unpacks the vertices and resolves the quads' corners.
+    shape: the volume's (depth, H, W), or just (H, W) -- the corner numbers are read with it.  vertices (nv, 3) int32 in
+    zyx order, quads (nq, 4) int32 (-1 where the keys hold no vertex for a corner: keys that are not a whole volume's),
+    objects (n, 5) int64: label, v_begin, v_end, q_begin, q_end.  nv or nq of 2^31 or more is a ValueError.  One host
+    sync (the object count).  info: a dict that receives 'work_bytes' (workspace of the sorts and the index)."""
+    name = "mesh_finish"
+    try:
+        qkeys, qdirs = quads
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: quads must be label_mesh's pair (qkeys, qdirs)") from None
+    keys = _mesh_operand(name, "keys", keys, torch.int64)
+    dev = keys.device
+    qkeys = _mesh_operand(name, "qkeys", qkeys, torch.int64, device=dev)
+    qdirs = _mesh_operand(name, "qdirs", qdirs, torch.int32, device=dev)
+    if keys.dim() != 1 or qkeys.dim() != 1 or qdirs.shape != qkeys.shape:
+        raise ValueError(f"{name}: keys (nv,), qkeys (nq,) and qdirs (nq,) expected, got {tuple(keys.shape)}, "
+                         f"{tuple(qkeys.shape)} and {tuple(qdirs.shape)}")
+    H, W = (_mesh_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
+    if (H + 1) * (W + 1) > MESH_MAX_CORNERS:
+        raise ValueError(f"{name}: slices of {H} x {W} voxels have more than 2^32 corners")
+    nv, nq = keys.numel(), qkeys.numel()
+    if nv > MESH_MAX_ITEMS or nq > MESH_MAX_ITEMS:
+        raise ValueError(f"{name}: {nv} vertices and {nq} quads: each must stay below 2^31 (int32 indices)")
+    vertices = torch.empty((nv, 3), dtype=torch.int32, device=dev)
+    out = torch.empty((nq, 4), dtype=torch.int32, device=dev)
+    stats = {} if info is None else info
+    stats.update(work_bytes=0)
+    if nv == 0 and nq == 0:
+        return vertices, out, torch.zeros((0, MESH_OBJECT_COLUMNS), dtype=torch.int64, device=dev)
+    require_gpu()
+    with torch.cuda.device(dev):
+        if nv:
+            keys = sort_u64_i32(keys, torch.zeros((nv,), dtype=torch.int32, device=dev))[0]
+        if nq:
+            qkeys, qdirs = sort_u64_i32(qkeys, qdirs, 32, 64)
+        cap = nv // 4 + 1                   # a label owns at least the four corners of one voxel face
+        objects = torch.empty((cap, MESH_OBJECT_COLUMNS), dtype=torch.int64, device=dev)
+        n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+        wb = query('emp_label_mesh_index_work_bytes', nv)
+        work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+        stats['work_bytes'] = int(wb) + int(query('emp_sort_work_bytes', max(nv, nq))) + 12 * max(nv, nq)
+        call('emp_label_mesh_index', _ptr(keys), nv, _ptr(qkeys), _ptr(qdirs), nq, H, W, _ptr(work), wb, _ptr(vertices),
+             _ptr(out), _ptr(objects), cap, _ptr(n_out), _current_stream(), alg_bytes=20 * nv + 28 * nq)
+        n = int(n_out.item())
+    if n > cap:
+        raise HipError(f"{name}: {n} labels among {nv} keys: these are not the keys of label_mesh")
+    return vertices, out, objects[:n].clone()
+
+
+def mesh_neighbours(vertices, quads):
+    """(nv, 6) int32 table of a mesh's lattice neighbours, one slot per direction code, -1 = none (emp_mesh_neighbours)"""
+    name = "mesh_neighbours"
+    vertices = _mesh_operand(name, "vertices", vertices, torch.int32)
+    quads = _mesh_operand(name, "quads", quads, torch.int32, device=vertices.device)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or quads.dim() != 2 or quads.shape[1] != 4:
+        raise ValueError(f"{name}: vertices (nv, 3) and quads (nq, 4) expected, got {tuple(vertices.shape)} and "
+                         f"{tuple(quads.shape)}")
+    nbr = torch.empty((vertices.shape[0], 6), dtype=torch.int32, device=vertices.device)
+    if vertices.shape[0]:
+        require_gpu()
+        with torch.cuda.device(vertices.device):
+            call('emp_mesh_neighbours', _ptr(vertices), vertices.shape[0], _ptr(quads), quads.shape[0], _ptr(nbr),
+                 _current_stream())
+    return nbr
+
+
+def mesh_smooth(vertices, quads, iterations, lam=0.5, mu=-0.53):
+    """Taubin smoothing of a mesh on the device: (nv, 3) float32 positions after `iterations` rounds of p <- p + lam (m -
+    p), then p <- p + mu (m - p), m the mean of a vertex's lattice neighbours (at most six, added in the order of the
+    direction codes).  vertices (nv, 3) int32 and quads (nq, 4) int32 as mesh_finish returns them.  Every object is
+    smoothed by itself, so touching objects may drift apart or overlap by a fraction of a voxel.  0 iterations: the
+    integer positions as float32."""
+    import numbers
+    name = "mesh_smooth"
+    iterations = _mesh_int(name, "iterations", iterations, 0)
+    for what, v in (("lam", lam), ("mu", mu)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not -1.0 <= float(v) <= 1.0:
+            raise ValueError(f"{name}: {what} must be a number in -1 .. 1, got {v!r}")
+    nbr = mesh_neighbours(vertices, quads)
+    p = vertices.to(torch.float32)
+    nv = p.shape[0]
+    if nv == 0 or iterations == 0:
+        return p
+    q = torch.empty_like(p)
+    with torch.cuda.device(p.device):
+        for _ in range(iterations):
+            call('emp_mesh_smooth', _ptr(p), _ptr(nbr), nv, float(lam), _ptr(q), _current_stream(), alg_bytes=48 * nv)
+            call('emp_mesh_smooth', _ptr(q), _ptr(nbr), nv, float(mu), _ptr(p), _current_stream(), alg_bytes=48 * nv)
+    return p
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -443,6 +443,61 @@ def _measured(res, spacing, labels, class_names, out, group):
     return res
 
 
+def _check_mesh(mesh):
+    """infer_volume's `mesh` argument -> None or the number of smoothing iterations, before any GPU work"""
+    from ..meshes import check
+    return check(mesh)
+
+
+def mesh_dataset_names(classes, class_names):
+    return {c: {k: f"{(class_names or {}).get(c, c)}_mesh_{k}" for k in ('vertices', 'quads', 'objects')} for c in classes}
+
+
+def _meshed(res, iterations, thing_list, shape3d, class_names, out, group):
+    """the result with 'meshes': every rank emits its slab of every thing class (meshes.mesh_volume, z_base = z0) with
+    the neighbouring ranks' end slices, every rank finishes the same whole mesh, and rank 0 writes three datasets per
+    class"""
+    if iterations is None:
+        return res
+    from ..meshes import OBJECT_COLUMNS, mesh_volume
+    rank, world = sharded._world(group)
+    z0 = int(res['z_range'][0])
+    classes = [c for c in res['volumes'] if c in thing_list]
+    meshes = {}
+    for c in classes:
+        m = mesh_volume(res['volumes'][c], group, z0, int(shape3d[0]), iterations)
+        meshes[c] = {k: v.cpu().numpy() for k, v in m.items()}
+    res['meshes'] = meshes
+    if out is None:
+        return res
+    names = mesh_dataset_names(classes, class_names)
+    left_out = set()
+    if rank == 0:
+        for c in classes:
+            try:
+                for k, a in meshes[c].items():
+                    ds = out.create_dataset(names[c][k], shape=a.shape, dtype=a.dtype, overwrite=True,
+                                            chunks=(max(a.shape[0], 1), a.shape[1]))
+                    if a.shape[0]:
+                        ds[...] = a
+            except Exception:
+                if meshes[c]['objects'].shape[0]:
+                    raise
+                left_out.add(c)                      # a store that cannot hold a zero-row array
+        attrs = {'meshes': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS), 'iterations': int(iterations)}}
+        if isinstance(out, ZarrV2Group):
+            out.update_attrs(attrs)
+        elif hasattr(out, 'attrs'):
+            out.attrs.update(attrs)
+    if world > 1:
+        flag = [sorted(left_out, key=str)]
+        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
+        left_out = set(flag[0])
+    res['mesh_datasets'] = {c: None if c in left_out else {k: out[names[c][k]] for k in names[c]} for c in classes}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -470,7 +525,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None, split_objects=None, fill_holes=None, morph=None, separate=None):
+                 measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -562,6 +617,20 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     Datasets, compressed output, pyramid, scores and measurements see the new labels; stuff classes stay as they are.
     'instances' grow by the pieces added and the result gains 'separated': {class: {'r2', 'min_core', 'sampling',
     'objects_in', 'objects_separated', 'pieces_added', 'voxels_moved', 'sweeps'}}, the same on every rank.
+    mesh: None = no mesh, no new key, no launch; True, or a non-negative integer n = once the volumes are final (after
+    morph, separate, split_objects and fill_holes, where measure runs) every thing class gets one welded, outward-
+    oriented quad mesh of its objects' exposed voxel faces, built on the device (meshes.mesh_volume; include/emp_hip.h,
+    E7): every rank emits its slab with the end slices of the ranks next to it, and every rank finishes the same whole
+    mesh.  n > 0 adds n Taubin smoothing iterations on the device; every object is smoothed by itself, so touching
+    objects may drift apart or overlap by a fraction of a voxel.  The result gains 'meshes': {class: {'vertices':
+    (nv, 3) in zyx order, int32 lattice corners (True, 0) or float32 (n > 0), 'quads': (nq, 4) int32 vertex indices,
+    'objects': (n, 5) int64 rows of label, v_begin, v_end, q_begin, q_end, ascending by label -- the rows of measure's
+    table, whose columns 11..13 count the same faces}} as numpy arrays (meshes.triangles, meshes.object_mesh and
+    meshes.write_obj read them).  With out=, rank 0 writes '<class name>_mesh_vertices', '<class name>_mesh_quads'
+    and '<class name>_mesh_objects', the group's attributes gain 'meshes': {'axes': 'zyx', 'object_columns',
+    'iterations'}, and the result gains 'mesh_datasets': {class: {'vertices', 'quads', 'objects'}, or None where the
+    store cannot hold the zero-row arrays of a class without objects}.  A volume of more than 2^32 lattice corners
+    (about 1624^3), or a mesh of 2^31 vertices or quads, is a ValueError.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -572,6 +641,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     fill_wanted, fill_cap = _check_fill(fill_holes)
     morph = _check_morph(morph)
     separate = _check_separate(separate)
+    mesh_iterations = _check_mesh(mesh)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -639,7 +709,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
             res['split'] = split
         if fill_wanted:
             res['filled'] = filled
-        return _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
+        res = _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
+        return _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,

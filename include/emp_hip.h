@@ -922,6 +922,69 @@ int emp_label_grow_sweep(const void *lab, int item, int64_t D, int64_t H, int64_
 int emp_label_grow_paint(const uint64_t *state, const void *lab, int item, int64_t n, const uint32_t *lut,
                          int64_t n_lut, int mode, void *dst, int dst_item, void *stream);
 
+/* ---- E7: surface meshes of a label volume (welded, outward-oriented quads of the exposed voxel faces) ---------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact, object by object:
+ *          skimage.measure.marching_cubes or zmesh over a volume that was already resident.
+ * lab is a contiguous (D, H, W) array as in E2 (item = 1 or 4, 0 = background), with E2's optional neighbour slices
+ * `below` (z = -1) and `above` (z = D); a position outside the array reads as 0.
+ * Lattice.  Voxel (z, y, x) occupies [z, z + 1] x [y, y + 1] x [x, x + 1].  A corner is an integer point (z, y, x) with
+ *   0 <= z <= depth, 0 <= y <= H, 0 <= x <= W, and its number is (z_base + z) (H + 1) (W + 1) + y (W + 1) + x.
+ * Faces.  Label L != 0 owns one quad for every face of one of its voxels that E2 calls exposed: the voxel on the other
+ *   side has a different value.  A face between two different labels gives two quads, one per label, with opposite
+ *   windings.  Per object and axis the number of quads equals columns 11..13 of E2's table.
+ * Winding.  Every quad starts at its lowest corner o; with ez, ey, ex the unit steps its corners are, in order,
+ *     -z (0)  o, o+ex, o+ey+ex, o+ey        +z (1)  o, o+ey, o+ey+ex, o+ex
+ *     -y (2)  o, o+ez, o+ez+ex, o+ex        +y (3)  o, o+ex, o+ex+ez, o+ez
+ *     -x (4)  o, o+ey, o+ez+ey, o+ez        +x (5)  o, o+ez, o+ez+ey, o+ey
+ *   (the number is the direction code).  The arbiter: with vertices as (z, y, x) triples, the sum over an object's quads
+ *   of det[p0, p1, p2] + det[p0, p2, p3] is exactly 6 x the object's voxel count.
+ * Vertices.  One per (label, corner) pair that at least one of the label's quads touches; equivalently, of the eight
+ *   voxels around the corner at least one is L and at least one is not.  A corner can carry up to eight vertices.  Two
+ *   voxels of L that meet only along an edge or at a corner share those vertices, so an edge may carry four quads of
+ *   one object; it is not split.
+ * Order.  Vertices ascend by (label as unsigned, z, y, x): by the key label << 32 | corner.  Quads ascend by (label,
+ *   z, y, x of the owning voxel, direction code).  Both are fixed by the definition: bit-identical from run to run and
+ *   from any z-partition whose blocks were given their true neighbour slices.
+ * Outputs.  vertices (nv, 3) int32 in zyx order; quads (nq, 4) int32, indices into vertices; objects (n, 5) int64 --
+ *   label, v_begin, v_end, q_begin, q_end -- ascending by label, the rows of E2's table.
+ * Limits, refused with EMP_EINVAL and never truncated: (depth + 1) (H + 1) (W + 1) <= 2^32 for the whole volume (the
+ *   key holds the corner in 32 bits; about 1624^3), nv and nq below 2^31, and D H W <= 2^26 per call of steps 1 and 2
+ *   (6 quads and 8 keys per voxel seen at most: the int32 scan stays exact) -- callers cut z-blocks.
+ * A block owns the corner planes 0 .. D - 1 and, with `top` (the volume's last block), plane D: a seam plane is emitted
+ * once, by the block above it, which sees the same eight voxels through `below`.
+ * Step 1  emp_label_mesh_count: R = D H + (D + top) (H + 1) rows -- the voxel rows, then the owned corner rows -- and
+ *         row_offsets[0..R] (R + 1 int32) = exclusive prefix sum of the quads per voxel row and the keys per corner
+ *         row: row_offsets[D H] is the quad total n_quads, row_offsets[R] - n_quads the key total n_keys.  work:
+ *         emp_label_mesh_count_work_bytes(R) bytes.
+ * Step 2  emp_label_mesh_emit: vkeys[n_keys] = label << 32 | corner in corner order; per quad qkeys = label << 32 | its
+ *         lowest corner o and qdirs = its direction code, in (z, y, x, direction) order.  The labels must not have
+ *         changed since step 1 (an item past the totals is dropped, never written).
+ * Step 3  the caller sorts vkeys over all 64 bits and (qkeys, qdirs) stably over bits 32..63 (emp_sort_u64_i32); keys
+ *         and quads of several blocks or ranks are concatenated in z order first.
+ * Step 4  emp_label_mesh_index: sorted keys -> vertices and objects (at most max_objects rows are written; n_objects,
+ *         a device int32, receives the number of labels), sorted quads -> quads, each corner found by a binary search
+ *         inside its object's [v_begin, v_end); -1 where the keys hold no such vertex.  work:
+ *         emp_label_mesh_index_work_bytes(nv) bytes.
+ * No step uses atomics and no order depends on scheduling.
+ * Smoothing.  Every quad edge joins two lattice neighbours, so a vertex has at most six neighbours, one per direction
+ *   code.  emp_mesh_neighbours fills nbr (nv, 6) int32, -1 = none.  emp_mesh_smooth is one step dst = src + factor (m -
+ *   src) over (nv, 3) float32, m the mean of the present neighbours added in slot order; src and dst must differ.  One
+ *   Taubin iteration is a step with lambda = 0.5 and one with mu = -0.53.  Each object is smoothed by itself: touching
+ *   objects may drift apart or overlap by a fraction of a voxel.                                                       */
+int64_t emp_label_mesh_count_work_bytes(int64_t R);
+int emp_label_mesh_count(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below,
+                         const void *above, int top, void *work, int64_t work_bytes, int32_t *row_offsets, void *stream);
+int emp_label_mesh_emit(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
+                        int top, int64_t z_base, const int32_t *row_offsets, int64_t n_quads, int64_t n_keys,
+                        uint64_t *vkeys, uint64_t *qkeys, int32_t *qdirs, void *stream);
+int64_t emp_label_mesh_index_work_bytes(int64_t nv);
+int emp_label_mesh_index(const uint64_t *vkeys, int64_t nv, const uint64_t *qkeys, const int32_t *qdirs, int64_t nq,
+                         int64_t H, int64_t W, void *work, int64_t work_bytes, int32_t *vertices, int32_t *quads,
+                         int64_t *objects, int64_t max_objects, int32_t *n_objects, void *stream);
+int emp_mesh_neighbours(const int32_t *vertices, int64_t nv, const int32_t *quads, int64_t nq, int32_t *nbr,
+                        void *stream);
+int emp_mesh_smooth(const float *src, const int32_t *nbr, int64_t nv, float factor, float *dst, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
