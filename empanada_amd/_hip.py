@@ -142,6 +142,17 @@ SIGNATURES = {
     'emp_label_mesh_emit': (_I, [_P, _I, _L, _L, _L, _P, _P, _I, _L, _P, _L, _L, _P, _P, _P, _P]),
     'emp_label_mesh_index_work_bytes': (_L, [_L]),
     'emp_label_mesh_index': (_I, [_P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P]),
+    'emp_skel_classify': (_I, [_P, _L, _P, _P]),
+    'emp_label_thin_work_bytes': (_L, [_L, _L, _L]),
+    'emp_label_thin_init': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P]),
+    'emp_label_thin_mark': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
+    'emp_label_thin_pass': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P]),
+    'emp_label_thin_paint': (_I, [_P, _P, _I, _L, _P, _I, _P]),
+    'emp_label_graph_count_work_bytes': (_L, [_L]),
+    'emp_label_graph_count': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _L, _P, _P]),
+    'emp_label_graph_emit': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P]),
+    'emp_label_graph_index_work_bytes': (_L, [_L]),
+    'emp_label_graph_index': (_I, [_P, _P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P]),
     'emp_mesh_neighbours': (_I, [_P, _L, _P, _L, _P, _P]),
     'emp_mesh_smooth': (_I, [_P, _P, _L, _F, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
@@ -1771,6 +1782,358 @@ def mesh_smooth(vertices, quads, iterations, lam=0.5, mu=-0.53):
             call('emp_mesh_smooth', _ptr(p), _ptr(nbr), nv, float(lam), _ptr(q), _current_stream(), alg_bytes=48 * nv)
             call('emp_mesh_smooth', _ptr(q), _ptr(nbr), nv, float(mu), _ptr(p), _current_stream(), alg_bytes=48 * nv)
     return p
+
+
+THIN_MAX_VOXELS = MEASURE_MAX_VOXELS         # voxels per emp_label_thin_* call
+GRAPH_MAX_VOXELS = 2 ** 26                   # voxels per emp_label_graph_count / _emit call: 14 items per voxel at most
+GRAPH_MAX_VOLUME = 2 ** 32                   # voxels of the whole volume: the key holds the voxel number in 32 bits
+GRAPH_MAX_ITEMS = 2 ** 31 - 1                # vertices, and edges, of one graph: int32 indices
+GRAPH_OBJECT_COLUMNS = 8
+
+
+def skel_classify(masks):
+    """bit 0 = simple, bit 1 = isthmus of every 26-bit neighbourhood mask (emp_skel_classify; include/emp_hip.h, E8):
+    the predicate of the thinning passes, by the same device function.  masks: a 1-D contiguous int32 / uint32 tensor
+    on the GPU (bits 26 .. 31 are ignored); returns a uint8 tensor of its length."""
+    name = "skel_classify"
+    masks = _mesh_operand(name, "masks", masks, (torch.int32, torch.uint32))
+    if masks.dim() != 1:
+        raise ValueError(f"{name}: masks must be one-dimensional, got {tuple(masks.shape)}")
+    out = torch.empty((masks.numel(),), dtype=torch.uint8, device=masks.device)
+    if masks.numel():
+        require_gpu()
+        with torch.cuda.device(masks.device):
+            call('emp_skel_classify', _ptr(masks), masks.numel(), _ptr(out), _current_stream())
+    return out
+
+
+def _thin_operand(what, t, dtypes, shape=None, device=None):
+    try:
+        return _grow_operand(what, t, dtypes, shape, device)
+    except ValueError as e:
+        raise ValueError(str(e).replace("label_grow:", "label_thin:", 1)) from None
+
+
+def _thin_int(what, value, lo, hi):
+    import numbers
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
+        raise ValueError(f"label_thin: {what} must be an integer in {lo} .. {hi}, got {value!r}")
+    return int(value)
+
+
+def _thin_halo(slab, what, pair):
+    """None, or the checked (labels, state) pair of ONE (H, W) slice each that stands beside `slab`"""
+    if pair is None:
+        return None
+    H, W = int(slab.shape[1]), int(slab.shape[2])
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise ValueError(f"label_thin: {what} must be None or (labels, state): one (H, W) slice of each")
+    return (_thin_operand(f"{what}'s labels", pair[0], (slab.dtype,), (H, W), slab.device),
+            _thin_operand(f"{what}'s state", pair[1], (torch.uint8,), (H, W), slab.device))
+
+
+class LabelThin:
+    """The thinning of one slab in steps (include/emp_hip.h, E8): it keeps the slab, `state` -- the (D, H, W) uint8
+    tensor, bit 0 alive, bit 1 kept, bit 2 marked -- and the tile lists of the slab's z-blocks on the device.
+    mark(below, above) and run_pass(s, below, above) are steps 1 and 2 of an iteration, for a driver that runs several
+    slabs of one volume in lock-step; below / above are None (the volume's face) or (labels, state), ONE (H, W) slice
+    each of the neighbouring slab, as ends() hands them out.  deleted() reads the counters (one host read);
+    iterate(below, above) is mark, the eight passes and deleted() for a slab whose halo does not change in between.
+    `iterations` counts the marks, `voxels_deleted` what deleted() has seen so far."""
+
+    def __init__(self, slab, z_base=0, block_voxels=None, info=None):
+        slab = _thin_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+        if slab.dim() != 3:
+            raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+        D, H, W = (int(s) for s in slab.shape)
+        self.z_base = _thin_int("z_base", z_base, 0, 2 ** 62)
+        block_voxels = THIN_MAX_VOXELS if block_voxels is None else _thin_int("block_voxels", block_voxels, 1,
+                                                                               THIN_MAX_VOXELS)
+        if H * W > block_voxels:
+            raise ValueError(f"label_thin: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                             f"{int(block_voxels)} voxels per call; there is no split within a slice")
+        per = max(1, block_voxels // max(H * W, 1))
+        self.slab, self.iterations, self.voxels_deleted = slab, 0, 0
+        self._stats = {} if info is None else info
+        self._stats.update(blocks=-(-D // per), iterations=0, launches=0, active_tiles=0, work_bytes=slab.numel())
+        self._blocks = []
+        self.state = torch.empty((D, H, W), dtype=torch.uint8, device=slab.device)
+        if slab.numel() == 0:
+            return
+        require_gpu()
+        item = slab.element_size()
+        with torch.cuda.device(slab.device):
+            for z0 in range(0, D, per):
+                z1 = min(D, z0 + per)
+                wb = query('emp_label_thin_work_bytes', z1 - z0, H, W)
+                if wb < 0:
+                    raise ValueError(f"label_thin: {z1 - z0} x {H} x {W} voxels exceed the limit of {THIN_MAX_VOXELS} per call")
+                work = torch.empty((wb,), dtype=torch.uint8, device=slab.device)
+                self._stats['work_bytes'] += int(wb)
+                call('emp_label_thin_init', _ptr(slab[z0:z1]), item, z1 - z0, H, W, _ptr(self.state[z0:z1]), _ptr(work), wb,
+                     _current_stream(), alg_bytes=(z1 - z0) * H * W * (item + 1))
+                self._blocks.append(dict(z0=z0, z1=z1, work=work, listed=0))
+            for b, c in zip(self._blocks, self._counters()):      # one sync: the lengths of the lists
+                b['listed'] = c[0]
+                self._stats['active_tiles'] += b['listed']
+
+    def _counters(self):
+        """[list length, voxels deleted] of every z-block, in one host read"""
+        if not self._blocks:
+            return []
+        return torch.stack([b['work'][:16].view(torch.int64) for b in self._blocks]).tolist()
+
+    def _halo(self, what, pair):
+        return _thin_halo(self.slab, what, pair)
+
+    def ends(self):
+        """((labels, state) of the first slice, (labels, state) of the last one): what the slab's neighbours take as
+        their `above` and `below`; views into the live state.  None for an empty slab."""
+        if self.slab.shape[0] == 0:
+            return None
+        return (self.slab[0], self.state[0]), (self.slab[-1], self.state[-1])
+
+    def _step(self, name, below, above, *tail):
+        below, above = self._halo("below", below), self._halo("above", above)
+        slab, state = self.slab, self.state
+        D, H, W = (int(s) for s in slab.shape)
+        item = slab.element_size()
+        with torch.cuda.device(slab.device):
+            for b in self._blocks:
+                if b['listed'] == 0:
+                    continue
+                z0, z1 = b['z0'], b['z1']
+                lo = below if z0 == 0 else (slab[z0 - 1], state[z0 - 1])
+                hi = above if z1 == D else (slab[z1], state[z1])
+                args = [a(b, lo, hi) if callable(a) else a for a in tail]
+                call(name, _ptr(slab[z0:z1]), item, z1 - z0, H, W, _ptr(state[z0:z1]),
+                     _ptr(lo[0]) if lo else None, _ptr(lo[1]) if lo else None, _ptr(hi[0]) if hi else None,
+                     _ptr(hi[1]) if hi else None, _ptr(b['work']), b['work'].numel(), b['listed'], *args,
+                     _current_stream())
+                self._stats['launches'] += 1
+
+    def mark(self, below=None, above=None):
+        """step 1 of a new iteration"""
+        self.iterations += 1
+        self._stats['iterations'] = self.iterations
+        self._step('emp_label_thin_mark', below, above,
+                   lambda b, lo, hi: (1 if lo is not None else 0) | (2 if hi is not None else 0))
+
+    def run_pass(self, subfield, below=None, above=None):
+        """step 2 for sub-field 0 .. 7"""
+        subfield = _thin_int("subfield", subfield, 0, 7)
+        self._step('emp_label_thin_pass', below, above, subfield, lambda b, lo, hi: self.z_base + b['z0'])
+
+    def deleted(self):
+        """the voxels deleted since the last call: one host read of all z-blocks' counters"""
+        total = sum(c[1] for c in self._counters())
+        fresh = total - self.voxels_deleted
+        self.voxels_deleted = total
+        return fresh
+
+    def iterate(self, below=None, above=None):
+        """one whole iteration; returns the number of voxels it deleted"""
+        self.mark(below, above)
+        for s in range(8):
+            self.run_pass(s, below, above)
+        return self.deleted()
+
+    def paint(self, out=None, dtype=None):
+        """S = alive ? L : 0 as a (D, H, W) tensor: a fresh one of `dtype` (None: the slab's), or `out` -- the slab
+        itself (in place) or a contiguous uint8 / int32 / uint32 tensor on its device that does not overlap it."""
+        slab = self.slab
+        if out is None:
+            odt = slab.dtype if dtype is None else dtype
+            if odt not in (torch.uint8, torch.int32, torch.uint32):
+                raise ValueError(f"label_thin: dtype must be torch.uint8, int32 or uint32, got {odt}")
+            out = torch.empty(tuple(slab.shape), dtype=odt, device=slab.device)
+        else:
+            if dtype is not None and dtype != out.dtype:
+                raise ValueError(f"label_thin: dtype={dtype} given together with an out of {out.dtype}")
+            _thin_operand("out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), slab.device)
+        if out.element_size() == 1 and slab.element_size() == 4 and slab.numel():
+            bits = slab.view(torch.int32)
+            if int(bits.min()) < 0 or int(bits.max()) > 255:
+                raise ValueError("label_thin: the slab holds labels above 255, which a 1-byte output cannot hold")
+        with torch.cuda.device(slab.device):
+            for b in self._blocks:
+                z0, z1 = b['z0'], b['z1']
+                n = self.state[z0:z1].numel()
+                call('emp_label_thin_paint', _ptr(self.state[z0:z1]), _ptr(slab[z0:z1]), slab.element_size(), n,
+                     _ptr(out[z0:z1]), out.element_size(), _current_stream(),
+                     alg_bytes=n * (1 + slab.element_size() + out.element_size()))
+        return out
+
+
+def label_thin(slab, below=None, above=None, z_base=0, block_voxels=None, max_iterations=None, info=None):
+    """The skeleton S of a label slab (emp_label_thin_*; the definition is in include/emp_hip.h, E8): topological
+    thinning that keeps 1-D isthmuses, by sub-fields, as a new tensor of the slab's shape and dtype with S = L on the
+    voxels that stay and 0 elsewhere.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are
+    taken as they are).  below / above: None (the volume's face) or (labels, state) -- ONE (H, W) slice each of a
+    neighbouring slab that does not change during the call.  z_base: the slab's first slice in the volume; its parity
+    decides the sub-fields.  A slab of more than block_voxels voxels (None: THIN_MAX_VOXELS, the kernel's limit) is cut
+    into z-blocks of whole slices that read each other's end slices of state in place, so the result is the undivided
+    slab's.  max_iterations: None = max(D, H, W) + 2, and reaching that without settling is a RuntimeError; an explicit
+    limit that is reached stops the thinning and returns the volume as it then is, without an error.  One host read of
+    the counters per iteration.  Every argument error is a ValueError before any GPU work.  info: a dict that receives
+    'blocks', 'iterations', 'launches', 'voxels_deleted', 'active_tiles' (listed tiles) and 'work_bytes' (state
+    included)."""
+    if max_iterations is not None:
+        max_iterations = _thin_int("max_iterations", max_iterations, 1, 2 ** 62)
+    if below is not None or above is not None:                    # checked before anything is allocated
+        slab = _thin_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+        if slab.dim() != 3:
+            raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+        _thin_halo(slab, "below", below), _thin_halo(slab, "above", above)
+    t = LabelThin(slab, z_base, block_voxels, info)
+    t._stats['voxels_deleted'] = 0
+    if t.slab.numel() == 0:
+        return t.paint()
+    limit = max(t.slab.shape) + 2 if max_iterations is None else max_iterations
+    while True:
+        fresh = t.iterate(below, above)
+        t._stats['voxels_deleted'] = t.voxels_deleted
+        if fresh == 0:
+            break
+        if t.iterations >= limit:
+            if max_iterations is None:
+                raise RuntimeError(f"label_thin: not settled after {limit} iterations")
+            break
+    return t.paint()
+
+
+def label_graph(skel, below=None, above=None, z_base=0, depth=None, block_voxels=None, info=None):
+    """The unsorted vertex and edge records of a sparse label slab (emp_label_graph_count / _emit; include/emp_hip.h,
+    E8): ((vkeys, vdeg), (ekeys, ecodes)) on the slab's device -- vkeys (nv,) int64, the bits of label << 32 | global
+    voxel number, and vdeg (nv,) int32, the vertex's number of 26-neighbours of its label, in voxel order; ekeys (ne,)
+    int64, label << 32 | the edge's lower voxel, and ecodes (ne,) int32, 0 .. 12, in (voxel, code) order.  graph_finish
+    turns them, or the concatenation in z order of those of several slabs, into the graph.  skel: (D, H, W),
+    contiguous, on the GPU, uint8 or int32 / uint32.  below / above: (H, W) tensors of the slab's dtype and device that
+    stand for the slices at z = -1 and z = D, None = background.  z_base: the slab's first slice in the volume; depth:
+    the volume's depth (None: z_base + D), which fixes nothing but the limit depth H W <= 2^32 -- a ValueError
+    otherwise.  A slab of more than block_voxels voxels (None: GRAPH_MAX_VOXELS, the kernels' limit) is cut into
+    z-blocks with their true neighbour slices.  One host sync per block (the two totals).  info: a dict that receives
+    'blocks', 'vertices', 'edges' and 'work_bytes' (largest workspace of one call)."""
+    name = "label_graph"
+    skel = _mesh_operand(name, "skel", skel)
+    if skel.dim() != 3:
+        raise ValueError(f"{name}: skel must be a (D, H, W) tensor, got {tuple(skel.shape)}")
+    D, H, W = (int(s) for s in skel.shape)
+    dev = skel.device
+    if below is not None:
+        below = _mesh_operand(name, "below", below, skel.dtype, (H, W), dev)
+    if above is not None:
+        above = _mesh_operand(name, "above", above, skel.dtype, (H, W), dev)
+    z_base = _mesh_int(name, "z_base", z_base, 0)
+    depth = z_base + D if depth is None else _mesh_int(name, "depth", depth, z_base + D)
+    if block_voxels is None:
+        block_voxels = GRAPH_MAX_VOXELS
+    elif _mesh_int(name, "block_voxels", block_voxels, 1) > GRAPH_MAX_VOXELS:
+        raise ValueError(f"{name}: block_voxels must lie in 1 .. {GRAPH_MAX_VOXELS}, got {block_voxels!r}")
+    stats = {} if info is None else info
+    stats.update(blocks=0, vertices=0, edges=0, work_bytes=0)
+
+    def none(dtype):
+        return torch.zeros((0,), dtype=dtype, device=dev)
+    empty = ((none(torch.int64), none(torch.int32)), (none(torch.int64), none(torch.int32)))
+    if skel.numel() == 0:
+        return empty
+    if depth * H * W > GRAPH_MAX_VOLUME:
+        raise ValueError(f"{name}: a volume of {depth} x {H} x {W} = {depth * H * W} voxels is above the limit of 2^32 = "
+                         f"{GRAPH_MAX_VOLUME} that the 32-bit voxel number of a key sets")
+    if H * W > block_voxels:
+        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    require_gpu()
+    item = skel.element_size()
+    per = max(1, int(block_voxels) // (H * W))
+    parts = [[], [], [], []]
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            part = skel[z0:z1]
+            lo = below if z0 == 0 else skel[z0 - 1]
+            hi = above if z1 == D else skel[z1]
+            d = z1 - z0
+            rows = d * H
+            wb = query('emp_label_graph_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((2 * rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_graph_count', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), _ptr(work), wb, _ptr(offs),
+                 _current_stream(), alg_bytes=d * H * W * item)
+            nv, total = (int(v) for v in offs[[rows, 2 * rows]].tolist())
+            ne = total - nv
+            stats['blocks'] += 1
+            stats['vertices'] += nv
+            stats['edges'] += ne
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb) + 4 * (2 * rows + 1))
+            if nv == 0:
+                continue
+            out = (torch.empty((nv,), dtype=torch.int64, device=dev), torch.empty((nv,), dtype=torch.int32, device=dev),
+                   torch.empty((ne,), dtype=torch.int64, device=dev), torch.empty((ne,), dtype=torch.int32, device=dev))
+            call('emp_label_graph_emit', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), z_base + z0, _ptr(offs), nv, ne,
+                 *(_ptr(t) for t in out), _current_stream(), alg_bytes=d * H * W * item + 12 * (nv + ne))
+            for p, t in zip(parts, out):
+                p.append(t)
+    if not parts[0]:
+        return empty
+    vk, vd, ek, ec = (p[0] if len(p) == 1 else torch.cat(p) for p in parts)
+    return (vk, vd), (ek, ec)
+
+
+def graph_finish(vertices, edges, shape, info=None):
+    """(vertices, degree, edges, objects, order) of E8 from label_graph's ((vkeys, vdeg), (ekeys, ecodes)) of a whole
+    volume -- of one slab, or of several concatenated in z order.  Both key arrays are sorted stably over the label
+    bits (sort_u64_i32); the vertices' sort carries a permutation, `order` (nv,) int32, so that any per-vertex attribute
+    a of the unsorted records travels as a[order] -- the degree does.  emp_label_graph_index then cuts the objects,
+    unpacks the vertices and resolves the edges' ends.  shape: the volume's (depth, H, W), or just (H, W).  vertices
+    (nv, 3) int32 zyx, degree (nv,) int32, edges (ne, 2) int32 with i < j (-1 where the keys hold no such vertex),
+    objects (n, 8) int64: label, v_begin, v_end, e_begin, e_end, isolated, ends, junctions.  nv or ne of 2^31 or more
+    is a ValueError.  One host sync (the object count).  info: a dict that receives 'work_bytes'."""
+    name = "graph_finish"
+    try:
+        (vkeys, vdeg), (ekeys, ecodes) = vertices, edges
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: label_graph's pairs (vkeys, vdeg) and (ekeys, ecodes) expected") from None
+    vkeys = _mesh_operand(name, "vkeys", vkeys, torch.int64)
+    dev = vkeys.device
+    vdeg = _mesh_operand(name, "vdeg", vdeg, torch.int32, device=dev)
+    ekeys = _mesh_operand(name, "ekeys", ekeys, torch.int64, device=dev)
+    ecodes = _mesh_operand(name, "ecodes", ecodes, torch.int32, device=dev)
+    if vkeys.dim() != 1 or vdeg.shape != vkeys.shape or ekeys.dim() != 1 or ecodes.shape != ekeys.shape:
+        raise ValueError(f"{name}: vkeys and vdeg (nv,), ekeys and ecodes (ne,) expected, got {tuple(vkeys.shape)}, "
+                         f"{tuple(vdeg.shape)}, {tuple(ekeys.shape)} and {tuple(ecodes.shape)}")
+    H, W = (_mesh_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
+    if H * W > GRAPH_MAX_VOLUME:
+        raise ValueError(f"{name}: slices of {H} x {W} voxels hold more than 2^32 voxels")
+    nv, ne = vkeys.numel(), ekeys.numel()
+    if nv > GRAPH_MAX_ITEMS or ne > GRAPH_MAX_ITEMS:
+        raise ValueError(f"{name}: {nv} vertices and {ne} edges: each must stay below 2^31 (int32 indices)")
+    out_v = torch.empty((nv, 3), dtype=torch.int32, device=dev)
+    out_e = torch.empty((ne, 2), dtype=torch.int32, device=dev)
+    stats = {} if info is None else info
+    stats.update(work_bytes=0)
+    if nv == 0 and ne == 0:
+        return (out_v, vdeg.clone(), out_e, torch.zeros((0, GRAPH_OBJECT_COLUMNS), dtype=torch.int64, device=dev),
+                torch.zeros((0,), dtype=torch.int32, device=dev))
+    require_gpu()
+    with torch.cuda.device(dev):
+        order = torch.arange(nv, dtype=torch.int32, device=dev)
+        if nv:
+            vkeys, order = sort_u64_i32(vkeys, order, 32, 64)
+            vdeg = vdeg[order.long()].contiguous()
+        if ne:
+            ekeys, ecodes = sort_u64_i32(ekeys, ecodes, 32, 64)
+        cap = nv + 1
+        objects = torch.empty((cap, GRAPH_OBJECT_COLUMNS), dtype=torch.int64, device=dev)
+        n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+        wb = query('emp_label_graph_index_work_bytes', nv)
+        work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+        stats['work_bytes'] = int(wb) + int(query('emp_sort_work_bytes', max(nv, ne))) + 12 * max(nv, ne)
+        call('emp_label_graph_index', _ptr(vkeys), _ptr(vdeg), nv, _ptr(ekeys), _ptr(ecodes), ne, H, W, _ptr(work), wb,
+             _ptr(out_v), _ptr(out_e), _ptr(objects), cap, _ptr(n_out), _current_stream(), alg_bytes=36 * nv + 28 * ne)
+        n = int(n_out.item())
+    return out_v, vdeg, out_e, objects[:n].clone(), order
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -498,6 +498,65 @@ def _meshed(res, iterations, thing_list, shape3d, class_names, out, group):
     return res
 
 
+def _check_skeleton(skeleton):
+    """infer_volume's `skeleton` argument -> None or (r_cap, cap, sampling), before any GPU work"""
+    from ..skeletons import check
+    return check(skeleton)
+
+
+SKELETON_KEYS = ('vertices', 'radius2', 'degree', 'edges', 'objects')
+
+
+def skeleton_dataset_names(classes, class_names):
+    return {c: {k: f"{(class_names or {}).get(c, c)}_skeleton_{k}" for k in SKELETON_KEYS} for c in classes}
+
+
+def _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group):
+    """the result with 'skeletons': the ranks thin every thing class in lock-step (skeletons.skeleton_volume, z0 = the
+    slab's first slice), every rank finishes the same whole graph, and rank 0 writes five datasets per class"""
+    if skeleton is None:
+        return res
+    from ..skeletons import OBJECT_COLUMNS, skeleton_volume
+    r_cap, cap, sampling = skeleton
+    rank, world = sharded._world(group)
+    z0 = int(res['z_range'][0])
+    classes = [c for c in res['volumes'] if c in thing_list]
+    skeletons = {}
+    for c in classes:
+        s = skeleton_volume(res['volumes'][c], group, z0, int(shape3d[0]), cap, sampling)
+        skeletons[c] = {k: s[k].cpu().numpy() for k in SKELETON_KEYS}
+    res['skeletons'] = skeletons
+    if out is None:
+        return res
+    names = skeleton_dataset_names(classes, class_names)
+    left_out = set()
+    if rank == 0:
+        for c in classes:
+            try:
+                for k, a in skeletons[c].items():
+                    ds = out.create_dataset(names[c][k], shape=a.shape, dtype=a.dtype, overwrite=True,
+                                            chunks=(max(a.shape[0], 1),) + tuple(a.shape[1:]))
+                    if a.shape[0]:
+                        ds[...] = a
+            except Exception:
+                if skeletons[c]['objects'].shape[0]:
+                    raise
+                left_out.add(c)                      # a store that cannot hold a zero-row array
+        attrs = {'skeletons': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS), 'r_cap': float(r_cap),
+                               'sampling': [int(a) for a in sampling]}}
+        if isinstance(out, ZarrV2Group):
+            out.update_attrs(attrs)
+        elif hasattr(out, 'attrs'):
+            out.attrs.update(attrs)
+    if world > 1:
+        flag = [sorted(left_out, key=str)]
+        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
+        left_out = set(flag[0])
+    res['skeleton_datasets'] = {c: None if c in left_out else {k: out[names[c][k]] for k in names[c]} for c in classes}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -525,7 +584,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  min_size=500, min_span=4, pixel_vote_thr=2, cluster_iou_thr=0.75, bypass=False, class_names=None,
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
-                 measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None):
+                 measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None,
+                 skeleton=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -631,6 +691,18 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     'iterations'}, and the result gains 'mesh_datasets': {class: {'vertices', 'quads', 'objects'}, or None where the
     store cannot hold the zero-row arrays of a class without objects}.  A volume of more than 2^32 lattice corners
     (about 1624^3), or a mesh of 2^31 vertices or quads, is a ValueError.
+    skeleton: None = no skeleton, no new key, no launch; True, r_cap or (r_cap, (az, ay, ax)) (skeletons.check; r_cap,
+    default 64, is the largest radius reported, in the units of the sampling) = once the volumes are final, where mesh
+    and measure run, every thing class is thinned to the centrelines of its objects on the device -- topological
+    thinning that keeps 1-D isthmuses, by sub-fields (skeletons.skeleton_volume; include/emp_hip.h, E8) -- with the
+    ranks in lock-step, one end slice of state exchanged per side and pass.  An object with a cavity keeps a closed
+    shell around it, so fill_holes= belongs in front.  The result gains 'skeletons': {class: {'vertices': (nv, 3) int32
+    zyx, 'radius2': (nv,) int32 capped squared distance to the object's surface in the final volume, 'degree': (nv,)
+    int32, 'edges': (ne, 2) int32, 'objects': (n, 8) int64 rows of label, v_begin, v_end, e_begin, e_end, isolated,
+    ends, junctions}} as numpy arrays (skeletons.derive, skeletons.object_skeleton and skeletons.write_obj read them).
+    With out=, rank 0 writes '<class name>_skeleton_vertices', '_radius2', '_degree', '_edges' and '_objects', the
+    group's attributes gain 'skeletons': {'axes': 'zyx', 'object_columns', 'r_cap', 'sampling'}, and the result gains
+    'skeleton_datasets' as 'mesh_datasets'.  A volume above 2^32 voxels is a ValueError.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -642,6 +714,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     morph = _check_morph(morph)
     separate = _check_separate(separate)
     mesh_iterations = _check_mesh(mesh)
+    skeleton = _check_skeleton(skeleton)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -710,7 +783,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         if fill_wanted:
             res['filled'] = filled
         res = _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
-        return _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
+        res = _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
+        return _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group)
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,

@@ -985,6 +985,97 @@ int emp_mesh_neighbours(const int32_t *vertices, int64_t nv, const int32_t *quad
                         void *stream);
 int emp_mesh_smooth(const float *src, const int32_t *nbr, int64_t nv, float factor, float *dst, void *stream);
 
+/* ---- E8: skeletons of a label volume (thinning that keeps 1-D isthmuses, by sub-fields) and their graph -------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact, object by object: kimimaro or
+ *          skimage.morphology.skeletonize over a volume that was already resident.
+ * Setting.  L is a label volume (D, H, W), item = 1 or 4, 0 = background, the bits taken as they are (E2-E7).  The
+ *   object of a voxel v is the set of alive voxels with v's label; other labels, deleted voxels, 0 and positions outside
+ *   the volume are background for v.  Every voxel carries two bits: alive, initially L != 0, and kept, initially 0.
+ * Neighbourhood mask.  M(v) has 26 bits; bit n is set iff the neighbour at offset (dz, dy, dx) is alive and has v's
+ *   label; offsets are numbered in ascending (dz, dy, dx) order from (-1, -1, -1), skipping the centre:
+ *   n = 9 (dz + 1) + 3 (dy + 1) + (dx + 1), minus 1 past the centre.
+ * Predicates.  c26 = the number of 26-connected components of the set bits (two positions are adjacent iff they differ
+ *   by at most 1 in every coordinate).  t6: take the clear bits among the 18 face and edge positions, form components
+ *   under 6-adjacency among those 18 positions, count those that contain one of the 6 face positions.  v is SIMPLE iff
+ *   c26 = 1 and t6 = 1 (Bertrand-Malandain, (26, 6)); v is an ISTHMUS iff c26 >= 2.
+ * Schedule.  Iteration k = 1, 2, ...:
+ *   1. Mark.  Every alive voxel with a face neighbour that is not in its object is marked as border for this iteration.
+ *   2. Sub-fields.  For s = 0 .. 7 in this order, s = (Z & 1) << 2 | (y & 1) << 1 | (x & 1), Z the GLOBAL slice number
+ *      z_base + z: every voxel of sub-field s that is alive, marked and not kept is examined on the current state.  An
+ *      isthmus is set kept (for good; it stays), else a simple voxel is deleted, else it stays as it is and may be
+ *      examined again in a later iteration.
+ *   3. Stop after the first iteration in which no voxel was deleted, on any block or rank.
+ *   Two voxels of one sub-field are never 26-adjacent, so the decisions of a pass do not depend on one another or on
+ *   their order: the parallel schedule equals the sequential one, and in-place byte stores are race-free.
+ * Result.  S = alive ? L : 0.  S is a subset of L; per label the 26-components, enclosed cavities and tunnels are those
+ *   of L; a ball ends as one voxel; a solid with a cavity keeps a closed shell around it.  NOT idempotent: thinning S
+ *   again starts with no kept voxel and eats the curves from their ends.
+ * emp_skel_classify   out[i] = bit 0 simple | bit 1 isthmus of masks[i] (bits 26 .. 31 ignored): the device function
+ *                     that the pass uses.
+ * `state` is one uint8 per voxel, owned by the caller: bit 0 alive, bit 1 kept, bit 2 this iteration's mark.  It is
+ * the interface between passes, z-blocks and ranks.  `work` (emp_label_thin_work_bytes; -1 for a shape that a call
+ * would refuse) holds the list of tiles (8 x 8 x 64 voxels) that hold a labelled voxel, two byte arrays of due tiles
+ * and the counters: uint64 at work + 0 = length of the list, at work + 8 = voxels deleted since the initialisation,
+ * the only atomic of the passes.  Layout, every part on the next multiple of 256 bytes, n = ceil(D / 8) ceil(H / 8)
+ * ceil(W / 64) tiles: the two counters; list, n int32; n bytes, 1 = the tile is due for the next mark; n bytes, 1 = the
+ * tile is due for the passes (written by the mark step, cleared by a pass that leaves no candidate).  A call covers at most 2^31 - 1 voxels; every argument error is EMP_EINVAL before any
+ * launch; D == 0 is a no-op.  below / above: ONE slice each of (labels, state) of the neighbouring z-block or rank,
+ * both null = the volume's face.
+ * emp_label_thin_init   writes every state byte, the list, and marks every listed tile as due for the first mark.
+ * emp_label_thin_mark   step 1 over the due tiles, one workgroup per listed tile (n_listed = the list's length): a tile
+ *                       is due when a voxel of it or of its ring was deleted since it was last marked; force bit 0 / 1
+ *                       runs the tiles on the first / last slice whatever the flags say (the halo may have changed).
+ *                       A tile that then holds no alive, marked, not-kept voxel is not due for the passes.
+ * emp_label_thin_pass   step 2 for one sub-field, one workgroup per listed tile; tile and ring are staged in LDS.  A
+ *                       deletion makes the tile and every tile whose ring holds the voxel (faces, edges, corners) due
+ *                       for the next mark.
+ * emp_label_thin_paint  dst = alive ? L : 0 over n voxels, item size 1 or 4; dst may be the labels themselves.
+ * Graph of a sparse label volume S (whatever made it).  Vertices: every voxel with S != 0, key = label << 32 | global
+ *   voxel number ((z_base + z) H + y) W + x, ascending by (label unsigned, z, y, x).  Edges: one per unordered pair of
+ *   26-adjacent voxels of one label, owned by the lower voxel, for the 13 offsets lexicographically above (0, 0, 0),
+ *   codes 0 .. 12 in ascending (dz, dy, dx); ascending by (label, lower voxel, code).  A block owns the edges whose lower
+ *   end it owns, so edges need only `above`; the degree of a vertex, the number of its 26-neighbours of its label, is
+ *   read at emit time and needs both.
+ * Step 1  emp_label_graph_count: R = D H rows; row_offsets[0 .. 2 R] (2 R + 1 int32) = exclusive prefix sum of the
+ *         vertices per row, then of the edges per row: row_offsets[R] = nv, row_offsets[2 R] - nv = ne.  D H W <= 2^26
+ *         per call.  work: emp_label_graph_count_work_bytes(R) bytes.
+ * Step 2  emp_label_graph_emit: vkeys / vdeg (nv) in voxel order, ekeys = label << 32 | lower voxel / ecodes (ne) in
+ *         (voxel, code) order; an item past the totals is dropped, never written.
+ * Step 3  the caller sorts both key arrays stably over bits 32 .. 63 (emp_sort_u64_i32), blocks and ranks concatenated
+ *         in z order first; vertex attributes travel as a sorted permutation.
+ * Step 4  emp_label_graph_index: vertices (nv, 3) int32 zyx global, edges (ne, 2) int32 with i < j, each end found by
+ *         binary search inside its object's [v_begin, v_end), -1 where the keys hold no such vertex; objects (n, 8)
+ *         int64: label, v_begin, v_end, e_begin, e_end, isolated (degree 0), ends (degree 1), junctions (degree >= 3);
+ *         at most max_objects rows are written, n_objects (device int32) receives the number of labels.  work:
+ *         emp_label_graph_index_work_bytes(nv) bytes.
+ * No step of the graph uses atomics: bit-identical from run to run and from any z-partition.  Refused, never truncated:
+ * a whole volume above 2^32 voxels, nv or ne of 2^31 or more.                                                        */
+int emp_skel_classify(const uint32_t *masks, int64_t n, uint8_t *out, void *stream);
+int64_t emp_label_thin_work_bytes(int64_t D, int64_t H, int64_t W);
+int emp_label_thin_init(const void *lab, int item, int64_t D, int64_t H, int64_t W, uint8_t *state, void *work,
+                        int64_t work_bytes, void *stream);
+int emp_label_thin_mark(const void *lab, int item, int64_t D, int64_t H, int64_t W, uint8_t *state,
+                        const void *below_lab, const uint8_t *below_state, const void *above_lab,
+                        const uint8_t *above_state, void *work, int64_t work_bytes, int64_t n_listed, int force,
+                        void *stream);
+int emp_label_thin_pass(const void *lab, int item, int64_t D, int64_t H, int64_t W, uint8_t *state,
+                        const void *below_lab, const uint8_t *below_state, const void *above_lab,
+                        const uint8_t *above_state, void *work, int64_t work_bytes, int64_t n_listed, int subfield,
+                        int64_t z_base, void *stream);
+int emp_label_thin_paint(const uint8_t *state, const void *lab, int item, int64_t n, void *dst, int dst_item,
+                         void *stream);
+int64_t emp_label_graph_count_work_bytes(int64_t R);
+int emp_label_graph_count(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below,
+                          const void *above, void *work, int64_t work_bytes, int32_t *row_offsets, void *stream);
+int emp_label_graph_emit(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
+                         int64_t z_base, const int32_t *row_offsets, int64_t nv, int64_t ne, uint64_t *vkeys,
+                         int32_t *vdeg, uint64_t *ekeys, int32_t *ecodes, void *stream);
+int64_t emp_label_graph_index_work_bytes(int64_t nv);
+int emp_label_graph_index(const uint64_t *vkeys, const int32_t *vdeg, int64_t nv, const uint64_t *ekeys,
+                          const int32_t *ecodes, int64_t ne, int64_t H, int64_t W, void *work, int64_t work_bytes,
+                          int32_t *vertices, int32_t *edges, int64_t *objects, int64_t max_objects, int32_t *n_objects,
+                          void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
