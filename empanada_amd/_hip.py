@@ -153,6 +153,14 @@ SIGNATURES = {
     'emp_label_graph_emit': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _P]),
     'emp_label_graph_index_work_bytes': (_L, [_L]),
     'emp_label_graph_index': (_I, [_P, _P, _L, _P, _P, _L, _L, _L, _P, _L, _P, _P, _P, _L, _P, _P]),
+    'emp_label_contacts_work_bytes': (_L, [_L, _L, _L]),
+    'emp_label_contacts_count': (_I, [_P, _I, _P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P, _L, _P,
+                                      _P]),
+    'emp_label_contacts_emit': (_I, [_P, _I, _P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P, _L, _L,
+                                     _L, _P, _P, _P, _P]),
+    'emp_label_contacts_rows_work_bytes': (_L, [_L]),
+    'emp_label_contacts_rows': (_I, [_P, _L, _P, _L, _P, _P]),
+    'emp_label_contacts_reduce': (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
     'emp_mesh_neighbours': (_I, [_P, _L, _P, _L, _P, _P]),
     'emp_mesh_smooth': (_I, [_P, _P, _L, _F, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
@@ -2134,6 +2142,197 @@ def graph_finish(vertices, edges, shape, info=None):
              _ptr(out_v), _ptr(out_e), _ptr(objects), cap, _ptr(n_out), _current_stream(), alg_bytes=36 * nv + 28 * ne)
         n = int(n_out.item())
     return out_v, vdeg, out_e, objects[:n].clone(), order
+
+
+CONTACT_MAX_HALO = 4                         # ring of the staged tile, in voxels: isqrt(r2) // min(sampling) at most
+CONTACTS_MAX_VOXELS = 2 ** 28                # voxels per z-block of label_contacts by default (the kernel takes 2^31 - 1)
+CONTACTS_MAX_RECORDS = 2 ** 31 - 1           # records of one emp_label_contacts_emit call: refused above, never truncated
+CONTACTS_BLOCK_RECORDS = 2 ** 27             # above this a z-block of several slices is halved: ~45 bytes per record
+CONTACT_COLUMNS = 10
+
+
+def contact_ball(r2, sampling=(1, 1, 1)):
+    """The ball of E9 as an (n, 4) int32 numpy array of (dz, dy, dx, d2): the offsets with d2 = (az dz)^2 + (ay dy)^2 +
+    (ax dx)^2 <= r2 in ascending (d2, dz, dy, dx)."""
+    import math
+    import numpy as np
+    az, ay, ax = (int(a) for a in sampling)
+    root = math.isqrt(int(r2))
+    hz, hy, hx = root // az, root // ay, root // ax
+    dz, dy, dx = np.meshgrid(np.arange(-hz, hz + 1), np.arange(-hy, hy + 1), np.arange(-hx, hx + 1), indexing='ij')
+    d2 = (az * dz) ** 2 + (ay * dy) ** 2 + (ax * dx) ** 2
+    keep = d2 <= int(r2)
+    rows = np.stack([dz[keep], dy[keep], dx[keep], d2[keep]], axis=1)
+    order = np.lexsort((rows[:, 2], rows[:, 1], rows[:, 0], rows[:, 3]))
+    return np.ascontiguousarray(rows[order], dtype=np.int32)
+
+
+def _contacts_operand(what, t, dtype=None, shape=None):
+    """dtype, shape and layout of an operand; where it lives is checked last, so that a test without a GPU reaches these"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"label_contacts: {what} must be a tensor, got {type(t).__name__}")
+    dtypes = (torch.uint8, torch.int32, torch.uint32) if dtype is None else (dtype,)
+    if t.dtype not in dtypes:
+        raise ValueError(f"label_contacts: {what} has dtype {t.dtype}, expected one of {dtypes}")
+    if t.dim() != 3 or (shape is not None and tuple(t.shape[1:]) != tuple(shape)):
+        raise ValueError(f"label_contacts: {what} must be a (D, H, W) tensor" +
+                         (f" with (H, W) = {tuple(shape)}" if shape is not None else "") + f", got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"label_contacts: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    return t
+
+
+def _contacts_r2(r2, sampling):
+    import math
+    sampling = _morph_sampling('label_contacts', sampling)
+    r2 = _morph_bound('label_contacts', "r2", r2, 1, 2 ** 24 - 1)
+    if r2 < min(sampling) ** 2:
+        raise ValueError(f"label_contacts: r2 = {r2} is below the smallest squared pitch of {sampling}: the ball is a "
+                         "point")
+    if math.isqrt(r2) // min(sampling) > CONTACT_MAX_HALO:
+        raise ValueError(f"label_contacts: r2 = {r2} at sampling {sampling} reaches {math.isqrt(r2) // min(sampling)} "
+                         f"voxels, above the ring of {CONTACT_MAX_HALO} (CONTACT_MAX_HALO)")
+    return r2, sampling
+
+
+def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, z_base=0, block_voxels=None, info=None):
+    """The contact table of two label slabs, or of one with itself (emp_label_contacts_*; the definition is in
+    include/emp_hip.h, E9): an (n, 10) int64 table on the slab's device, one row per ordered pair (a, b) of labels with a
+    voxel of a within the ball of squared radius r2 of a voxel of b, ascending by (a, b) -- a, b, voxels, min_d2, sum_z
+    sum_y sum_x, faces_z faces_y faces_x (contacts.COLUMNS).  a, b: contiguous (D, H, W) GPU tensors of equal shape and
+    device, each uint8 or int32 / uint32 on its own (the bits are taken as they are); b=None is the same-volume case,
+    which leaves out b == a.  sampling: the voxel pitch (az, ay, ax), integers in 1 .. 16; min(sampling)^2 <= r2 and
+    isqrt(r2) // min(sampling) <= CONTACT_MAX_HALO.  below / above: (h, H, W) stacks of B's dtype and device, h <=
+    isqrt(r2) // az, that stand for B at z = -h .. -1 and z = D .. D + h - 1, None = the volume's face (label_edt's
+    convention); z_base is added to every z index.  A slab of more than block_voxels voxels (None:
+    CONTACTS_MAX_VOXELS) is cut into z-blocks of whole slices, B's halo slices taken as views of the slab, and a block
+    whose records exceed CONTACTS_BLOCK_RECORDS is halved again; the block tables are merged on the device
+    (contacts.merge_tables).  A single slice of 2^31 records or more is a ValueError.  Every argument error, a CPU tensor
+    among them, is a ValueError before any launch.  Empty or all-zero inputs give a (0, 10) table.  info: a dict that
+    receives 'blocks' (z-blocks walked), 'tiles' (tiles listed), 'records' and 'work_bytes' (largest workspaces of one
+    block, records included)."""
+    import math
+    import numbers
+    r2, sampling = _contacts_r2(r2, sampling)
+    az, ay, ax = sampling
+    a = _contacts_operand("a", a)
+    D, H, W = (int(s) for s in a.shape)
+    dev = a.device
+    same = b is None
+    if same:
+        b = a
+    else:
+        b = _contacts_operand("b", b)
+        if tuple(b.shape) != (D, H, W):
+            raise ValueError(f"label_contacts: b is {tuple(b.shape)}, a is {(D, H, W)}: the shapes must be equal")
+    halo = math.isqrt(r2) // az
+    for what, t in (("below", below), ("above", above)):
+        if t is not None:
+            _contacts_operand(what, t, b.dtype, (H, W))
+            if int(t.shape[0]) > halo:
+                raise ValueError(f"label_contacts: {what} holds {int(t.shape[0])} slices, the ball reaches {halo}")
+    for what, t in (("a", a), ("b", b), ("below", below), ("above", above)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"label_contacts: {what} is on {t.device}: expected a tensor on the GPU")
+        if t is not None and t.device != dev:
+            raise ValueError(f"label_contacts: {what} is on {t.device}, a on {dev}")
+    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
+        raise ValueError(f"label_contacts: z_base must be a non-negative integer, got {z_base!r}")
+    if block_voxels is None:
+        block_voxels = CONTACTS_MAX_VOXELS
+    else:
+        block_voxels = _morph_bound('label_contacts', "block_voxels", block_voxels, 1, MEASURE_MAX_VOXELS)
+    stats = {} if info is None else info
+    stats.update(blocks=0, tiles=0, records=0, work_bytes=0)
+    empty = torch.zeros((0, CONTACT_COLUMNS), dtype=torch.int64, device=dev)
+    if a.numel() == 0:
+        return empty
+    if H * W > block_voxels:
+        raise ValueError(f"label_contacts: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{block_voxels} voxels per call; there is no split within a slice")
+    require_gpu()
+    per = max(1, block_voxels // (H * W))
+    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
+    bits = (lambda t: t.view(torch.int32)) if b.dtype == torch.uint32 else (lambda t: t)   # torch copies few uint32 tensors
+
+    def stack(lo, hi):
+        """B's slices [lo, hi), continued by the caller's stacks beyond the slab's ends: (tensor or None, slices)"""
+        parts = []
+        if lo < 0 and n_below:
+            parts.append(below[max(n_below + lo, 0):])
+        if max(lo, 0) < min(hi, D):
+            parts.append(b[max(lo, 0):min(hi, D)])
+        if hi > D and n_above:
+            parts.append(above[:min(hi - D, n_above)])
+        parts = [p for p in parts if p.shape[0]]
+        if not parts:
+            return None, 0
+        if len(parts) == 1:
+            return parts[0], int(parts[0].shape[0])
+        both = torch.cat([bits(p) for p in parts])
+        return both.view(b.dtype), int(both.shape[0])
+
+    tables = []
+    with torch.cuda.device(dev):
+        ball = torch.from_numpy(contact_ball(r2, sampling)).to(dev)
+        n_ball = int(ball.shape[0])
+        todo = [(z0, min(D, z0 + per)) for z0 in range(0, D, per)][::-1]
+        while todo:
+            z0, z1 = todo.pop()
+            d = z1 - z0
+            lo, hb = stack(z0 - halo, z0)
+            hi, ha = stack(z1, z1 + halo)
+            pa, pb = a[z0:z1], b[z0:z1]
+            geom = (_ptr(pa), pa.element_size(), _ptr(pb), pb.element_size(), d, H, W, _ptr(lo), hb, _ptr(hi), ha,
+                    1 if same else 0, az, ay, ax, r2, _ptr(ball), n_ball)
+            wb = query('emp_label_contacts_work_bytes', d, H, W)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            totals = torch.empty((2,), dtype=torch.int64, device=dev)
+            call('emp_label_contacts_count', *geom, _ptr(work), wb, _ptr(totals), _current_stream(),
+                 alg_bytes=d * H * W * (pa.element_size() + pb.element_size()))
+            n_listed, n = (int(v) for v in totals.tolist())
+            if d > 1 and n > CONTACTS_BLOCK_RECORDS:
+                mid = z0 + d // 2
+                todo += [(mid, z1), (z0, mid)]
+                continue
+            if n > CONTACTS_MAX_RECORDS:
+                raise ValueError(f"label_contacts: slice {z0} alone holds {n} records, above the limit of "
+                                 f"{CONTACTS_MAX_RECORDS} per call; there is no split within a slice")
+            stats['blocks'] += 1
+            stats['tiles'] += n_listed
+            stats['records'] += n
+            if n == 0:
+                stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+                continue
+            keys = torch.empty((n,), dtype=torch.int64, device=dev)
+            vox = torch.empty((n,), dtype=torch.int32, device=dev)
+            d2f = torch.empty((n,), dtype=torch.int32, device=dev)
+            call('emp_label_contacts_emit', *geom, _ptr(work), wb, n_listed, n, _ptr(keys), _ptr(vox), _ptr(d2f),
+                 _current_stream(), alg_bytes=d * H * W * (pa.element_size() + pb.element_size()) + 16 * n)
+            del work
+            order = torch.arange(n, dtype=torch.int32, device=dev)
+            skeys, perm = torch.empty_like(keys), torch.empty_like(order)
+            sb = query('emp_sort_work_bytes', n)
+            swork = torch.empty((sb,), dtype=torch.uint8, device=dev)
+            call('emp_sort_u64_i32', _ptr(keys), _ptr(skeys), _ptr(order), _ptr(perm), n, 0, 64, _ptr(swork), sb,
+                 _current_stream())
+            del keys, order, swork
+            rb = query('emp_label_contacts_rows_work_bytes', n)
+            rwork = torch.empty((rb,), dtype=torch.uint8, device=dev)
+            n_rows = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_contacts_rows', _ptr(skeys), n, _ptr(rwork), rb, _ptr(n_rows), _current_stream())
+            rows = int(n_rows.item())
+            table = torch.empty((rows, CONTACT_COLUMNS), dtype=torch.int64, device=dev)
+            call('emp_label_contacts_reduce', _ptr(skeys), _ptr(perm), _ptr(vox), _ptr(d2f), n, H, W, int(z_base) + z0,
+                 _ptr(rwork), rb, _ptr(table), rows, _current_stream())
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb) + int(sb) + int(rb) + 40 * n)
+            tables.append(table)
+    if not tables:
+        return empty
+    if len(tables) == 1:
+        return tables[0]
+    from .contacts import merge_tables
+    return merge_tables(tables)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -557,6 +557,79 @@ def _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group):
     return res
 
 
+def _check_contacts(contacts, labels, thing_list):
+    """infer_volume's `contacts` argument -> None or (r2, sampling, the class pairs in sorted order), before any GPU work"""
+    from ..contacts import check
+    checked = check(contacts)
+    if checked is None:
+        return None
+    r2, sampling, pairs = checked
+    if pairs is None:
+        pairs = [(c, c) for c in labels if c in thing_list] + [(c1, c2) for c1 in labels for c2 in labels if c1 != c2]
+    for ca, cb in pairs:
+        for c in (ca, cb):
+            if c not in labels:
+                raise ValueError(f"contacts: pairs name class {c!r}, the labels are {labels}")
+    return r2, sampling, sorted(set(pairs), key=lambda p: (labels.index(p[0]), labels.index(p[1])))
+
+
+def contact_dataset_names(pairs, class_names):
+    name = lambda c: (class_names or {}).get(c, c)
+    return {p: f"{name(p[0])}_{name(p[1])}_contacts" for p in pairs}
+
+
+def _contacted(res, contacts, class_names, out, group):
+    """the result with 'contacts': the ranks walk the class pairs in the same order; for each, every rank reads the
+    contact table of its slab of A (_hip.label_contacts, z_base = z0) against its slab of B with B's halo slices from the
+    ranks next to it (sharded.neighbour_slabs), the tables are merged over the ranks, and rank 0 writes one
+    '<class a name>_<class b name>_contacts' dataset per pair"""
+    if contacts is None:
+        return res
+    from ..contacts import COLUMNS, gather_tables, halo_slices
+    r2, sampling, pairs = contacts
+    rank, world = sharded._world(group)
+    z0 = int(res['z_range'][0])
+    halo = halo_slices(r2, sampling)
+    slabs = {c: res['volumes'][c].contiguous() for c in {c for p in pairs for c in p}}
+    tables = {}
+    for ca, cb in pairs:
+        below, above = sharded.neighbour_slabs(slabs[cb], halo, group)
+        table = _hip.label_contacts(slabs[ca], None if ca == cb else slabs[cb], r2, sampling, below=below, above=above,
+                                    z_base=z0)
+        tables[(ca, cb)] = gather_tables(table, group).cpu().numpy()
+    res['contacts'] = tables
+    res['contact_params'] = {'r2': int(r2), 'sampling': tuple(int(a) for a in sampling)}
+    if out is None:
+        return res
+    names = contact_dataset_names(pairs, class_names)
+    left_out = set()
+    if rank == 0:
+        for p in pairs:
+            table = tables[p]
+            try:
+                ds = out.create_dataset(names[p], shape=table.shape, dtype=np.int64, overwrite=True,
+                                        chunks=(max(table.shape[0], 1), table.shape[1]))
+                if table.shape[0]:
+                    ds[...] = table
+            except Exception:
+                if table.shape[0]:
+                    raise
+                left_out.add(p)                      # a store that cannot hold a zero-row array
+        attrs = {'contacts': {'columns': list(COLUMNS), 'r2': int(r2), 'sampling': [int(a) for a in sampling],
+                              'pairs': [[ca, cb] for ca, cb in pairs]}}
+        if isinstance(out, ZarrV2Group):
+            out.update_attrs(attrs)
+        elif hasattr(out, 'attrs'):
+            out.attrs.update(attrs)
+    if world > 1:
+        flag = [sorted(left_out, key=str)]
+        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
+        left_out = set(flag[0])
+    res['contact_datasets'] = {p: None if p in left_out else out[names[p]] for p in pairs}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -585,7 +658,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
                  measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None,
-                 skeleton=None):
+                 skeleton=None, contacts=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -703,6 +776,23 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     With out=, rank 0 writes '<class name>_skeleton_vertices', '_radius2', '_degree', '_edges' and '_objects', the
     group's attributes gain 'skeletons': {'axes': 'zyx', 'object_columns', 'r_cap', 'sampling'}, and the result gains
     'skeleton_datasets' as 'mesh_datasets'.  A volume above 2^32 voxels is a ValueError.
+    contacts: None = no table, no new key, no launch; r, (r, (az, ay, ax)) or (r, (az, ay, ax), pairs) (contacts.check; r is
+    the radius in the units of the sampling, integer voxel pitches in 1 .. 16, (1, 1, 1) by default; the ball may reach
+    4 voxels along the finest axis) = once the volumes are final, where measure, mesh and skeleton run, every pair of
+    classes (ca, cb) gets the table of the contact sites between the objects of ca and those of cb, read on the device
+    (_hip.label_contacts; include/emp_hip.h, E9): a voxel of object a is a contact voxel of (a, b) when a voxel of b lies
+    within r of it, every partner within r counting, not only the nearest.  pairs: a list of (class_a, class_b) from
+    `labels` (an unknown class is a ValueError before any work); by default (c, c) for every thing class -- the
+    instances of one class among each other -- and (c1, c2) for every ordered pair of distinct classes, stuff classes
+    included (a thing class against a semantic class is the main use).  The ranks walk the pairs in the same order;
+    every rank reads its z-slab of ca against its slab of cb with the few slices of cb that the ball reaches in the
+    ranks next to it, and the tables are merged over the ranks.  The result gains 'contacts': {(ca, cb): (n, 10) int64
+    numpy table of the WHOLE volume, the same on every rank, one row per ordered pair of labels (a, b) ascending:
+    contacts.COLUMNS -- a, b, voxels, min_d2, sum_z, sum_y, sum_x, faces_z, faces_y, faces_x} and 'contact_params':
+    {'r2', 'sampling'}, which contacts.derive turns into distances, centroids and shared areas.  With out=, rank 0 writes
+    one dataset '<class a name>_<class b name>_contacts' per pair (int64, (n, 10), one raw chunk), the group's
+    attributes gain 'contacts': {'columns', 'r2', 'sampling', 'pairs'}, and the result gains 'contact_datasets': {(ca,
+    cb): array, or None where the store cannot hold a zero-row table}.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -720,6 +810,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
     labels = list(labels)
     thing_list = list(engine.thing_list)
+    contacts = _check_contacts(contacts, labels, thing_list)
     div = engine.label_divisor
     factor = int(getattr(engine, 'padding_factor', 16))
     f = downsample_f
@@ -784,7 +875,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
             res['filled'] = filled
         res = _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
         res = _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
-        return _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group)
+        res = _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group)
+        return _contacted(res, contacts, class_names, out, group)
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,

@@ -1076,6 +1076,63 @@ int emp_label_graph_index(const uint64_t *vkeys, const int32_t *vdeg, int64_t nv
                           int32_t *vertices, int32_t *edges, int64_t *objects, int64_t max_objects, int32_t *n_objects,
                           void *stream);
 
+/* ---- E9: contact sites between labelled objects -- a table of the pairs that lie within a radius of each other ----------
+ * replaces, on the device, what users of the reference run on a CPU after the fact, object pair by object pair:
+ *          scipy.ndimage.distance_transform_edt or a dilation per object, then a comparison with every other object.
+ * Setting.  A and B are label volumes (D, H, W) of equal shape, each with item = 1 (uint8) or 4 (uint32; the bits of an
+ *   int32 are taken as they are, as in E2-E8); 0 is background.  B may be A itself (same = 1).  The voxel pitch
+ *   (az, ay, ax) is integers in 1 .. 16; r2 is an integer with min(pitch)^2 <= r2 and isqrt(r2) / min(pitch) <= 4
+ *   (CONTACT_MAX_HALO).  Anything else is refused.
+ * Ball.  The offsets o = (dz, dy, dx) with d2(o) = az^2 dz^2 + ay^2 dy^2 + ax^2 dx^2 <= r2, in ascending (d2, dz, dy,
+ *   dx); (0, 0, 0) is one of them; at unit pitch and r2 = 24 there are 485.  Nothing lies outside the volume: its faces
+ *   hold no candidates (as in E5).
+ * Contact voxel.  v is a contact voxel of the ordered pair (a, b) when A(v) = a != 0, b != 0, b != a in the same-volume
+ *   case, and some offset o of the ball has B(v + o) = b.  Its distance d2(v, b) is the smallest such d2(o).  One voxel
+ *   may be a contact voxel of many b; all of them count, not only the nearest.  With two volumes a voxel may be labelled
+ *   in both: d2 = 0, a contact.
+ * Table.  One row of 10 int64 per ordered pair (a, b) with at least one contact voxel, ascending by (a, b) as unsigned
+ *   32-bit values: a, b, voxels, min_d2, sum_z, sum_y, sum_x, faces_z, faces_y, faces_x.  voxels: the contact voxels of a
+ *   with b; min_d2: the smallest d2(v, b) among them; sum_*: their index sums, z_base added to z; faces_i: over those
+ *   voxels, the number of 6-neighbours along axis i that carry b in B, counted only when a_i^2 <= r2 (that neighbour
+ *   lies in the ball; with r2 >= max(pitch)^2 that is every a|b face).  Columns 2 and 4..9 are sums, column 3 is a
+ *   minimum, and every contact voxel belongs to the one z-block that owns v: tables of z-blocks and ranks merge exactly,
+ *   whatever the partition and the order.  In the same-volume case min_d2 and faces_* of (a, b) equal those of (b, a).
+ *   All results are exact integers, bit-identical from run to run and from any z-partition.
+ * The volume B may be continued along z by two halo stacks as in E5: `below` holds hb slices that stand for z = -hb ..
+ *   -1 and `above` ha slices for z = D .. D + ha - 1, of B's item size, hb, ha <= isqrt(r2) / az; 0 = the volume's face.
+ * ball: the table above on the device, n_ball rows of 4 int32 (dz, dy, dx, d2), built by the caller; a row that reaches
+ *   outside the ring (isqrt(r2) / pitch per axis) or whose d2 is not in 0 .. r2 is not walked, so no table makes a kernel
+ *   read outside its tile.
+ * Step 1  emp_label_contacts_count: flags the tiles (8 x 8 x 64 voxels) in which A has a label and B's tile plus ring
+ *         holds a possible partner, lists them, counts the records of every listed tile -- one per (contact voxel, b) --
+ *         and scans the counts.  totals (device int64[2]) receives the listed tiles and the records.  All of it stays in
+ *         `work` (emp_label_contacts_work_bytes; -1 for a shape that a call would refuse) for step 2.  A call covers at
+ *         most 2^31 - 1 voxels.
+ * Step 2  emp_label_contacts_emit: the same walk writes per record keys = a << 32 | b, vox = the voxel's number inside
+ *         the block and d2f = d2 << 6 | six face bits (bit 2 axis + side).  n_records >= 2^31 is refused, never
+ *         truncated: the caller cuts a smaller z-block.  The order of a tile's records is not fixed; the table is.
+ * Step 3  the caller sorts the keys over all 64 bits with emp_sort_u64_i32, carrying the permutation 0 .. n - 1.
+ * Step 4  emp_label_contacts_rows: heads of the runs of equal sorted keys and their scan, kept in `work`
+ *         (emp_label_contacts_rows_work_bytes); n_rows (device int32) receives the number of rows.
+ * Step 5  emp_label_contacts_reduce: with the same `work`, writes the n_rows rows of `table`; the sums and the minimum
+ *         are integer atomics, so no order shows in them.                                                             */
+int64_t emp_label_contacts_work_bytes(int64_t D, int64_t H, int64_t W);
+int emp_label_contacts_count(const void *a, int item_a, const void *b, int item_b, int64_t D, int64_t H, int64_t W,
+                             const void *below, int64_t hb, const void *above, int64_t ha, int same, int az, int ay,
+                             int ax, int r2, const int32_t *ball, int n_ball, void *work, int64_t work_bytes,
+                             int64_t *totals, void *stream);
+int emp_label_contacts_emit(const void *a, int item_a, const void *b, int item_b, int64_t D, int64_t H, int64_t W,
+                            const void *below, int64_t hb, const void *above, int64_t ha, int same, int az, int ay,
+                            int ax, int r2, const int32_t *ball, int n_ball, void *work, int64_t work_bytes,
+                            int64_t n_listed, int64_t n_records, uint64_t *keys, int32_t *vox, int32_t *d2f,
+                            void *stream);
+int64_t emp_label_contacts_rows_work_bytes(int64_t n);
+int emp_label_contacts_rows(const uint64_t *keys, int64_t n, void *work, int64_t work_bytes, int32_t *n_rows,
+                            void *stream);
+int emp_label_contacts_reduce(const uint64_t *keys, const int32_t *perm, const int32_t *vox, const int32_t *d2f,
+                              int64_t n, int64_t H, int64_t W, int64_t z_base, const void *work, int64_t work_bytes,
+                              int64_t *table, int64_t n_rows, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
