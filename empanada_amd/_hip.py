@@ -301,6 +301,64 @@ def _expect(what, t, dtype=None, shape=None, numel=None):
     return t
 
 
+# ------------------------------------------------------------------ what the labelled-volume stages share
+_LABEL_DTYPES = (torch.uint8, torch.int32, torch.uint32)
+
+
+def _label_operand(name, what, t, dtypes=None, shape=None, device=None):
+    """A stage's tensor operand: on the GPU, of one of `dtypes` (None: the label dtypes), of `shape` -- (None, H, W)
+    is a halo stack of any number of slices -- contiguous and on `device`; every miss is a ValueError."""
+    stack = shape is not None and shape[0] is None
+    try:
+        _expect(f"{name}: {what}", t, _LABEL_DTYPES if dtypes is None else dtypes, None if stack else shape)
+    except HipError as e:
+        raise ValueError(str(e)) from None
+    if stack and (t.dim() != 3 or tuple(t.shape[1:]) != tuple(shape[1:])):
+        raise ValueError(f"{name}: {what} must be a (h, {shape[1]}, {shape[2]}) stack, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
+    return t
+
+
+def _label_int(name, what, value, lo, hi=None):
+    import numbers
+    ok = not isinstance(value, bool) and isinstance(value, numbers.Integral) and value >= lo
+    if not ok or (hi is not None and value > hi):
+        raise ValueError(f"{name}: {what} must be an integer " + (f">= {lo}" if hi is None else f"in {lo} .. {hi}") +
+                         f", got {value!r}")
+    return int(value)
+
+
+def _block_voxels(name, block_voxels, limit):
+    """the voxels per call that a stage was asked for: None is the kernel's limit"""
+    import numbers
+    if block_voxels is None:
+        return limit
+    if (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
+            or not 1 <= block_voxels <= limit):
+        raise ValueError(f"{name}: block_voxels must lie in 1 .. {limit}, got {block_voxels!r}")
+    return int(block_voxels)
+
+
+def _block_slices(name, H, W, block_voxels):
+    """whole slices per call"""
+    if H * W > block_voxels:
+        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
+                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    return max(1, int(block_voxels) // max(H * W, 1))
+
+
+def _z_blocks(slab, below, above, per):
+    """The z-blocks of `per` slices of a slab, each with its true neighbour slices: (z0, z1, slab[z0:z1], the slice
+    under it, the slice over it) -- views of the slab, or below / above at its ends."""
+    D = int(slab.shape[0])
+    for z0 in range(0, D, per):
+        z1 = min(D, z0 + per)
+        yield z0, z1, slab[z0:z1], below if z0 == 0 else slab[z0 - 1], above if z1 == D else slab[z1]
+
+
 def median_harden_window(prob, ks, thr, hist=None, halo=None, want_tail=False, tail_out=None):
     """The recursive median + harden of a WINDOW of a longer stack (emp_median_harden_window).
     prob (D,C,H,W) fp32 cuda: the window's raw probabilities; hist (m,C,H,W), m = ks // 2: the filtered values of the m
@@ -747,18 +805,6 @@ MEASURE_MAX_VOXELS = 2 ** 31 - 1     # voxels per emp_label_measure call: one ru
 MEASURE_COLUMNS = 14
 
 
-def _measure_operand(what, t, dtype=None, shape=None, device=None):
-    try:
-        _expect(f"measure_labels: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
-    except HipError as e:
-        raise ValueError(str(e)) from None
-    if not t.is_contiguous():
-        raise ValueError(f"measure_labels: {what} must be contiguous (a copy would be a volume-sized allocation)")
-    if device is not None and t.device != device:
-        raise ValueError(f"measure_labels: {what} is on {t.device}, the slab on {device}")
-    return t
-
-
 def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, info=None):
     """Per-object measurements of a label slab (emp_label_measure; the definition is in include/emp_hip.h, E2): an
     (n, 14) int64 table on the slab's device, one row per distinct non-zero label, ascending by label -- label, voxels,
@@ -772,40 +818,29 @@ def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, in
     (0, 14) table.  Two host syncs per block (run count, label count).  info: a dict that receives 'blocks' (kernel
     calls made), 'runs' (runs they sorted) and 'work_bytes' (largest workspace of one call)."""
     import numbers
-    slab = _measure_operand("slab", slab)
+    slab = _label_operand("measure_labels", "slab", slab)
     if slab.dim() != 3:
         raise ValueError(f"measure_labels: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
     D, H, W = (int(s) for s in slab.shape)
     dev = slab.device
     if below is not None:
-        below = _measure_operand("below", below, slab.dtype, (H, W), dev)
+        below = _label_operand("measure_labels", "below", below, slab.dtype, (H, W), dev)
     if above is not None:
-        above = _measure_operand("above", above, slab.dtype, (H, W), dev)
+        above = _label_operand("measure_labels", "above", above, slab.dtype, (H, W), dev)
     if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
         raise ValueError(f"measure_labels: z_base must be a non-negative integer, got {z_base!r}")
-    if block_voxels is None:
-        block_voxels = MEASURE_MAX_VOXELS
-    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
-          or not 1 <= block_voxels <= MEASURE_MAX_VOXELS):
-        raise ValueError(f"measure_labels: block_voxels must lie in 1 .. {MEASURE_MAX_VOXELS}, got {block_voxels!r}")
+    block_voxels = _block_voxels("measure_labels", block_voxels, MEASURE_MAX_VOXELS)
     stats = {} if info is None else info
     stats.update(blocks=0, runs=0, work_bytes=0)
     empty = torch.zeros((0, MEASURE_COLUMNS), dtype=torch.int64, device=dev)
     if slab.numel() == 0:
         return empty
-    if H * W > block_voxels:
-        raise ValueError(f"measure_labels: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = _block_slices("measure_labels", H, W, block_voxels)
     require_gpu()
     item = slab.element_size()
-    per = max(1, int(block_voxels) // (H * W))
     tables = []
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            part = slab[z0:z1]
-            lo = below if z0 == 0 else slab[z0 - 1]
-            hi = above if z1 == D else slab[z1]
+        for z0, z1, part, lo, hi in _z_blocks(slab, below, above, per):
             d = z1 - z0
             rows = d * H
             wb = query('emp_label_measure_count_work_bytes', rows)
@@ -973,29 +1008,20 @@ def label_components(slab, connectivity=26, z_base=0, block_voxels=None, info=No
     dev = slab.device
     if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
         raise ValueError(f"label_components: z_base must be a non-negative integer, got {z_base!r}")
-    if block_voxels is None:
-        block_voxels = COMPONENTS_MAX_VOXELS
-    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
-          or not 1 <= block_voxels <= COMPONENTS_MAX_VOXELS):
-        raise ValueError(f"label_components: block_voxels must lie in 1 .. {COMPONENTS_MAX_VOXELS}, got {block_voxels!r}")
+    block_voxels = _block_voxels("label_components", block_voxels, COMPONENTS_MAX_VOXELS)
     stats = {} if info is None else info
     stats.update(blocks=0, runs=0, work_bytes=0)
     empty = torch.zeros((0, COMPONENT_COLUMNS), dtype=torch.int64, device=dev)
-    if H * W > block_voxels:
-        raise ValueError(f"label_components: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = _block_slices("label_components", H, W, block_voxels)
     if not slab.is_cuda:
         raise ValueError(f"label_components: slab is on {slab.device}, expected the GPU")
     if slab.numel() == 0:
         return LabelComponents(slab, connectivity, empty, [])
     require_gpu()
     item = slab.element_size()
-    per = max(1, int(block_voxels) // (H * W))
     blocks = []
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            part = slab[z0:z1]
+        for z0, z1, part, _, _ in _z_blocks(slab, None, None, per):
             d = z1 - z0
             rows = d * H
             wb = query('emp_label_measure_count_work_bytes', rows)
@@ -1049,18 +1075,6 @@ HOLES_MAX_VOXELS = MEASURE_MAX_VOXELS        # voxels per emp_label_holes call, 
 HOLE_COLUMNS = 10
 
 
-def _holes_operand(what, t, dtype=None, shape=None, device=None):
-    try:
-        _expect(f"label_holes: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
-    except HipError as e:
-        raise ValueError(str(e)) from None
-    if not t.is_contiguous():
-        raise ValueError(f"label_holes: {what} must be contiguous (a copy would be a volume-sized allocation)")
-    if device is not None and t.device != device:
-        raise ValueError(f"label_holes: {what} is on {t.device}, the slab on {device}")
-    return t
-
-
 class LabelHoles(LabelComponents):
     """What _hip.label_holes returns: `table`, the (n, 10) int64 cavity table on the slab's device (holes.COLUMNS), `n`,
     paint() and paint_slice().  It keeps the zero-run tables of the slab's blocks on the device, in the layout of
@@ -1096,40 +1110,29 @@ def label_holes(slab, below=None, above=None, z_base=0, block_voxels=None, info=
     import numbers
     if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
         raise ValueError(f"label_holes: z_base must be a non-negative integer, got {z_base!r}")
-    if block_voxels is None:
-        block_voxels = HOLES_MAX_VOXELS
-    elif (isinstance(block_voxels, bool) or not isinstance(block_voxels, numbers.Integral)
-          or not 1 <= block_voxels <= HOLES_MAX_VOXELS):
-        raise ValueError(f"label_holes: block_voxels must lie in 1 .. {HOLES_MAX_VOXELS}, got {block_voxels!r}")
-    slab = _holes_operand("slab", slab)
+    block_voxels = _block_voxels("label_holes", block_voxels, HOLES_MAX_VOXELS)
+    slab = _label_operand("label_holes", "slab", slab)
     if slab.dim() != 3:
         raise ValueError(f"label_holes: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
     D, H, W = (int(s) for s in slab.shape)
     dev = slab.device
     if below is not None:
-        below = _holes_operand("below", below, slab.dtype, (H, W), dev)
+        below = _label_operand("label_holes", "below", below, slab.dtype, (H, W), dev)
     if above is not None:
-        above = _holes_operand("above", above, slab.dtype, (H, W), dev)
+        above = _label_operand("label_holes", "above", above, slab.dtype, (H, W), dev)
     stats = {} if info is None else info
     stats.update(blocks=0, runs=0, work_bytes=0)
     empty = torch.zeros((0, HOLE_COLUMNS), dtype=torch.int64, device=dev)
-    if H * W > block_voxels:
-        raise ValueError(f"label_holes: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = _block_slices("label_holes", H, W, block_voxels)
     if not slab.is_cuda:
         raise ValueError(f"label_holes: slab is on {slab.device}, expected the GPU")
     if slab.numel() == 0:
         return LabelHoles(slab, empty, [])
     require_gpu()
     item = slab.element_size()
-    per = max(1, int(block_voxels) // (H * W))
     blocks = []
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            part = slab[z0:z1]
-            lo = below if z0 == 0 else slab[z0 - 1]
-            hi = above if z1 == D else slab[z1]
+        for z0, z1, part, lo, hi in _z_blocks(slab, below, above, per):
             d = z1 - z0
             rows = d * H
             wb = query('emp_label_holes_count_work_bytes', rows)
@@ -1194,27 +1197,6 @@ def _morph_sampling(name, sampling):
     return tuple(int(a) for a in vals)
 
 
-def _morph_bound(name, what, value, lo, hi):
-    import numbers
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
-        raise ValueError(f"{name}: {what} must be an integer in {lo} .. {hi}, got {value!r}")
-    return int(value)
-
-
-def _morph_operand(name, what, t, dtype=None, shape=None, device=None):
-    try:
-        _expect(f"{name}: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype)
-    except HipError as e:
-        raise ValueError(str(e)) from None
-    if shape is not None and (t.dim() != 3 or tuple(t.shape[1:]) != tuple(shape)):
-        raise ValueError(f"{name}: {what} must be a (h, {shape[0]}, {shape[1]}) stack, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
-    return t
-
-
 def _morph(name, slab, sampling, bound, below, above, block_voxels, info):
     """What label_edt, label_erode and label_dilate share: the checks, the cut into z-blocks with their halo stacks and
     the calls.  bound: cap - 1 for the distance, r2 for the others -- floor(sqrt(bound)) // az slices are all a block
@@ -1222,24 +1204,24 @@ def _morph(name, slab, sampling, bound, below, above, block_voxels, info):
     import math
     az, ay, ax = sampling = _morph_sampling(name, sampling)
     if name == 'label_edt':
-        limit = _morph_bound(name, "cap", bound, 1, 65535)
+        limit = _label_int(name, "cap", bound, 1, 65535)
         bound = limit - 1
     else:
-        limit = bound = _morph_bound(name, "r2", bound, 1, 65534)
+        limit = bound = _label_int(name, "r2", bound, 1, 65534)
         if bound < min(sampling) ** 2:
             raise ValueError(f"{name}: r2 = {bound} is below the smallest squared pitch of {sampling}: the ball is a "
                              "point")
     if block_voxels is not None:
-        block_voxels = _morph_bound(name, "block_voxels", block_voxels, 1, MORPH_MAX_VOXELS)
-    slab = _morph_operand(name, "slab", slab)
+        block_voxels = _label_int(name, "block_voxels", block_voxels, 1, MORPH_MAX_VOXELS)
+    slab = _label_operand(name, "slab", slab)
     if slab.dim() != 3:
         raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
     D, H, W = (int(s) for s in slab.shape)
     dev = slab.device
     if below is not None:
-        below = _morph_operand(name, "below", below, slab.dtype, (H, W), dev)
+        below = _label_operand(name, "below", below, slab.dtype, (None, H, W), dev)
     if above is not None:
-        above = _morph_operand(name, "above", above, slab.dtype, (H, W), dev)
+        above = _label_operand(name, "above", above, slab.dtype, (None, H, W), dev)
     stats = {} if info is None else info
     stats.update(blocks=0, work_bytes=0)
     out_dtype = torch.uint16 if name == 'label_edt' else slab.dtype
@@ -1339,27 +1321,20 @@ GROW_SWEEPS_PER_SYNC = 4                     # sweeps launched between two reads
 _GROW_SLOTS = 8
 
 
-def _grow_operand(what, t, dtypes, shape=None, device=None):
+def _grow_operand(name, what, t, dtypes, shape=None, device=None):
     if not isinstance(t, torch.Tensor):
-        raise ValueError(f"label_grow: {what} must be a tensor, got {type(t).__name__}")
+        raise ValueError(f"{name}: {what} must be a tensor, got {type(t).__name__}")
     if t.dtype not in dtypes:
-        raise ValueError(f"label_grow: {what} has dtype {t.dtype}, expected one of {dtypes}")
+        raise ValueError(f"{name}: {what} has dtype {t.dtype}, expected one of {dtypes}")
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"label_grow: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
+        raise ValueError(f"{name}: {what} is {tuple(t.shape)}, expected {tuple(shape)}")
     if not t.is_contiguous():
-        raise ValueError(f"label_grow: {what} must be contiguous (a copy would be a volume-sized allocation)")
+        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
     if not t.is_cuda:
-        raise ValueError(f"label_grow: {what} is on {t.device}, expected the GPU")
+        raise ValueError(f"{name}: {what} is on {t.device}, expected the GPU")
     if device is not None and t.device != device:
-        raise ValueError(f"label_grow: {what} is on {t.device}, the slab on {device}")
+        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
     return t
-
-
-def _grow_bound(what, value, lo, hi):
-    import numbers
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
-        raise ValueError(f"label_grow: {what} must be an integer in {lo} .. {hi}, got {value!r}")
-    return int(value)
 
 
 class LabelGrow:
@@ -1382,8 +1357,8 @@ class LabelGrow:
         H, W = int(self.slab.shape[1]), int(self.slab.shape[2])
         if not isinstance(pair, (tuple, list)) or len(pair) != 2:
             raise ValueError(f"label_grow: {what} must be None or (labels, state): one (H, W) slice of each")
-        return (_grow_operand(f"{what}'s labels", pair[0], (self.slab.dtype,), (H, W), self.slab.device),
-                _grow_operand(f"{what}'s state", pair[1], (torch.int64,), (H, W), self.slab.device))
+        return (_grow_operand("label_grow", f"{what}'s labels", pair[0], (self.slab.dtype,), (H, W), self.slab.device),
+                _grow_operand("label_grow", f"{what}'s state", pair[1], (torch.int64,), (H, W), self.slab.device))
 
     def ends(self):
         """((labels, state) of the first slice, (labels, state) of the last one): what the slab's neighbours take as
@@ -1488,7 +1463,7 @@ class LabelGrow:
         else:
             if dtype is not None and dtype != out.dtype:
                 raise ValueError(f"paint: dtype={dtype} given together with an out of {out.dtype}")
-            _grow_operand("out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), dev)
+            _grow_operand("label_grow", "out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), dev)
             odt = out.dtype
         item = 1 if odt == torch.uint8 else 4
         same = out is not None and out.data_ptr() == slab.data_ptr() and item == slab.element_size()
@@ -1537,22 +1512,19 @@ def label_grow(slab, seeds, below=None, above=None, block_voxels=None, max_sweep
     'sweeps' (launched), 'sweeps_needed' (per visit of a block, up to and including the first that stored nothing),
     'rounds', 'active_tiles' (listed tiles: those that hold a labelled voxel) and 'work_bytes' (state included); it
     keeps counting through resume()."""
-    slab = _grow_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+    slab = _grow_operand("label_grow", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
     if slab.dim() != 3:
         raise ValueError(f"label_grow: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
     D, H, W = (int(s) for s in slab.shape)
     dev = slab.device
-    seeds = _grow_operand("seeds", seeds, (torch.uint32, torch.int32), (D, H, W), dev)
+    seeds = _grow_operand("label_grow", "seeds", seeds, (torch.uint32, torch.int32), (D, H, W), dev)
     if block_voxels is None:
         block_voxels = GROW_MAX_VOXELS
     else:
-        block_voxels = _grow_bound("block_voxels", block_voxels, 1, GROW_MAX_VOXELS)
+        block_voxels = _label_int("label_grow", "block_voxels", block_voxels, 1, GROW_MAX_VOXELS)
     if max_sweeps is not None:
-        max_sweeps = _grow_bound("max_sweeps", max_sweeps, 1, 2 ** 62)
-    if H * W > block_voxels:
-        raise ValueError(f"label_grow: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
-    per = max(1, block_voxels // max(H * W, 1))
+        max_sweeps = _label_int("label_grow", "max_sweeps", max_sweeps, 1, 2 ** 62)
+    per = _block_slices("label_grow", H, W, block_voxels)
     n_blocks = -(-D // per)
     stats = {} if info is None else info
     stats.update(blocks=n_blocks, sweeps=0, sweeps_needed=0, rounds=0, active_tiles=0, work_bytes=0)
@@ -1568,14 +1540,13 @@ def label_grow(slab, seeds, below=None, above=None, block_voxels=None, max_sweep
     item = slab.element_size()
     with torch.cuda.device(dev):
         stats['work_bytes'] = g.state.numel() * 8
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
+        for z0, z1, part, _, _ in _z_blocks(slab, None, None, per):
             wb = query('emp_label_grow_work_bytes', z1 - z0, H, W)
             if wb < 0:
                 raise ValueError(f"label_grow: {z1 - z0} x {H} x {W} voxels exceed the limit of {GROW_MAX_VOXELS} per call")
             work = torch.empty((wb,), dtype=torch.uint8, device=dev)
             stats['work_bytes'] += int(wb)
-            call('emp_label_grow_init', _ptr(slab[z0:z1]), item, _ptr(seeds[z0:z1]), z1 - z0, H, W, _ptr(g.state[z0:z1]),
+            call('emp_label_grow_init', _ptr(part), item, _ptr(seeds[z0:z1]), z1 - z0, H, W, _ptr(g.state[z0:z1]),
                  _ptr(work), wb, _current_stream(), alg_bytes=(z1 - z0) * H * W * (item + 12))
             g._blocks.append(dict(z0=z0, z1=z1, work=work, turns=0, seen=[0] * _GROW_SLOTS, listed=0))
         for b in g._blocks:                                       # one sync: the lengths of the lists
@@ -1591,25 +1562,6 @@ MESH_MAX_VOXELS = 2 ** 26           # voxels per emp_label_mesh_count / _emit ca
 MESH_MAX_CORNERS = 2 ** 32          # corners of the whole volume: the key holds the corner number in 32 bits
 MESH_MAX_ITEMS = 2 ** 31 - 1        # vertices, and quads, of one mesh: int32 indices
 MESH_OBJECT_COLUMNS = 5
-
-
-def _mesh_operand(name, what, t, dtype=None, shape=None, device=None):
-    try:
-        _expect(f"{name}: {what}", t, (torch.uint8, torch.int32, torch.uint32) if dtype is None else dtype, shape)
-    except HipError as e:
-        raise ValueError(str(e)) from None
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: {what} must be contiguous (a copy would be a volume-sized allocation)")
-    if device is not None and t.device != device:
-        raise ValueError(f"{name}: {what} is on {t.device}, the slab on {device}")
-    return t
-
-
-def _mesh_int(name, what, value, lo):
-    import numbers
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value < lo:
-        raise ValueError(f"{name}: {what} must be an integer >= {lo}, got {value!r}")
-    return int(value)
 
 
 def label_mesh(slab, below=None, above=None, z_base=0, depth=None, top=True, block_voxels=None, info=None):
@@ -1628,22 +1580,22 @@ def label_mesh(slab, below=None, above=None, z_base=0, depth=None, top=True, blo
     One host sync per block (the two totals).  info: a dict that receives 'blocks' (kernel calls made), 'vertices',
     'quads' and 'work_bytes' (largest workspace of one call)."""
     name = "label_mesh"
-    slab = _mesh_operand(name, "slab", slab)
+    slab = _label_operand(name, "slab", slab)
     if slab.dim() != 3:
         raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
     D, H, W = (int(s) for s in slab.shape)
     dev = slab.device
     if below is not None:
-        below = _mesh_operand(name, "below", below, slab.dtype, (H, W), dev)
+        below = _label_operand(name, "below", below, slab.dtype, (H, W), dev)
     if above is not None:
-        above = _mesh_operand(name, "above", above, slab.dtype, (H, W), dev)
-    z_base = _mesh_int(name, "z_base", z_base, 0)
-    depth = z_base + D if depth is None else _mesh_int(name, "depth", depth, z_base + D)
+        above = _label_operand(name, "above", above, slab.dtype, (H, W), dev)
+    z_base = _label_int(name, "z_base", z_base, 0)
+    depth = z_base + D if depth is None else _label_int(name, "depth", depth, z_base + D)
     if not isinstance(top, (bool,)):
         raise ValueError(f"{name}: top must be True or False, got {top!r}")
     if block_voxels is None:
         block_voxels = MESH_MAX_VOXELS
-    elif _mesh_int(name, "block_voxels", block_voxels, 1) > MESH_MAX_VOXELS:
+    elif _label_int(name, "block_voxels", block_voxels, 1) > MESH_MAX_VOXELS:
         raise ValueError(f"{name}: block_voxels must lie in 1 .. {MESH_MAX_VOXELS}, got {block_voxels!r}")
     stats = {} if info is None else info
     stats.update(blocks=0, vertices=0, quads=0, work_bytes=0)
@@ -1654,19 +1606,12 @@ def label_mesh(slab, below=None, above=None, z_base=0, depth=None, top=True, blo
     if (depth + 1) * (H + 1) * (W + 1) > MESH_MAX_CORNERS:
         raise ValueError(f"{name}: a volume of {depth} x {H} x {W} voxels has {(depth + 1) * (H + 1) * (W + 1)} corners, "
                          f"above the limit of 2^32 = {MESH_MAX_CORNERS} that the 32-bit corner number of a key sets")
-    if H * W > block_voxels:
-        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = _block_slices(name, H, W, block_voxels)
     require_gpu()
     item = slab.element_size()
-    per = max(1, int(block_voxels) // (H * W))
     keys, qkeys, qdirs = [], [], []
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            part = slab[z0:z1]
-            lo = below if z0 == 0 else slab[z0 - 1]
-            hi = above if z1 == D else slab[z1]
+        for z0, z1, part, lo, hi in _z_blocks(slab, below, above, per):
             d = z1 - z0
             last = 1 if (top and z1 == D) else 0
             rows = d * H + (d + last) * (H + 1)
@@ -1711,14 +1656,14 @@ def mesh_finish(keys, quads, shape, info=None):
         qkeys, qdirs = quads
     except (TypeError, ValueError):
         raise ValueError(f"{name}: quads must be label_mesh's pair (qkeys, qdirs)") from None
-    keys = _mesh_operand(name, "keys", keys, torch.int64)
+    keys = _label_operand(name, "keys", keys, torch.int64)
     dev = keys.device
-    qkeys = _mesh_operand(name, "qkeys", qkeys, torch.int64, device=dev)
-    qdirs = _mesh_operand(name, "qdirs", qdirs, torch.int32, device=dev)
+    qkeys = _label_operand(name, "qkeys", qkeys, torch.int64, device=dev)
+    qdirs = _label_operand(name, "qdirs", qdirs, torch.int32, device=dev)
     if keys.dim() != 1 or qkeys.dim() != 1 or qdirs.shape != qkeys.shape:
         raise ValueError(f"{name}: keys (nv,), qkeys (nq,) and qdirs (nq,) expected, got {tuple(keys.shape)}, "
                          f"{tuple(qkeys.shape)} and {tuple(qdirs.shape)}")
-    H, W = (_mesh_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
+    H, W = (_label_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
     if (H + 1) * (W + 1) > MESH_MAX_CORNERS:
         raise ValueError(f"{name}: slices of {H} x {W} voxels have more than 2^32 corners")
     nv, nq = keys.numel(), qkeys.numel()
@@ -1753,8 +1698,8 @@ def mesh_finish(keys, quads, shape, info=None):
 def mesh_neighbours(vertices, quads):
     """(nv, 6) int32 table of a mesh's lattice neighbours, one slot per direction code, -1 = none (emp_mesh_neighbours)"""
     name = "mesh_neighbours"
-    vertices = _mesh_operand(name, "vertices", vertices, torch.int32)
-    quads = _mesh_operand(name, "quads", quads, torch.int32, device=vertices.device)
+    vertices = _label_operand(name, "vertices", vertices, torch.int32)
+    quads = _label_operand(name, "quads", quads, torch.int32, device=vertices.device)
     if vertices.dim() != 2 or vertices.shape[1] != 3 or quads.dim() != 2 or quads.shape[1] != 4:
         raise ValueError(f"{name}: vertices (nv, 3) and quads (nq, 4) expected, got {tuple(vertices.shape)} and "
                          f"{tuple(quads.shape)}")
@@ -1775,7 +1720,7 @@ def mesh_smooth(vertices, quads, iterations, lam=0.5, mu=-0.53):
     integer positions as float32."""
     import numbers
     name = "mesh_smooth"
-    iterations = _mesh_int(name, "iterations", iterations, 0)
+    iterations = _label_int(name, "iterations", iterations, 0)
     for what, v in (("lam", lam), ("mu", mu)):
         if isinstance(v, bool) or not isinstance(v, numbers.Real) or not -1.0 <= float(v) <= 1.0:
             raise ValueError(f"{name}: {what} must be a number in -1 .. 1, got {v!r}")
@@ -1804,7 +1749,7 @@ def skel_classify(masks):
     the predicate of the thinning passes, by the same device function.  masks: a 1-D contiguous int32 / uint32 tensor
     on the GPU (bits 26 .. 31 are ignored); returns a uint8 tensor of its length."""
     name = "skel_classify"
-    masks = _mesh_operand(name, "masks", masks, (torch.int32, torch.uint32))
+    masks = _label_operand(name, "masks", masks, (torch.int32, torch.uint32))
     if masks.dim() != 1:
         raise ValueError(f"{name}: masks must be one-dimensional, got {tuple(masks.shape)}")
     out = torch.empty((masks.numel(),), dtype=torch.uint8, device=masks.device)
@@ -1815,20 +1760,6 @@ def skel_classify(masks):
     return out
 
 
-def _thin_operand(what, t, dtypes, shape=None, device=None):
-    try:
-        return _grow_operand(what, t, dtypes, shape, device)
-    except ValueError as e:
-        raise ValueError(str(e).replace("label_grow:", "label_thin:", 1)) from None
-
-
-def _thin_int(what, value, lo, hi):
-    import numbers
-    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
-        raise ValueError(f"label_thin: {what} must be an integer in {lo} .. {hi}, got {value!r}")
-    return int(value)
-
-
 def _thin_halo(slab, what, pair):
     """None, or the checked (labels, state) pair of ONE (H, W) slice each that stands beside `slab`"""
     if pair is None:
@@ -1836,8 +1767,8 @@ def _thin_halo(slab, what, pair):
     H, W = int(slab.shape[1]), int(slab.shape[2])
     if not isinstance(pair, (tuple, list)) or len(pair) != 2:
         raise ValueError(f"label_thin: {what} must be None or (labels, state): one (H, W) slice of each")
-    return (_thin_operand(f"{what}'s labels", pair[0], (slab.dtype,), (H, W), slab.device),
-            _thin_operand(f"{what}'s state", pair[1], (torch.uint8,), (H, W), slab.device))
+    return (_grow_operand("label_thin", f"{what}'s labels", pair[0], (slab.dtype,), (H, W), slab.device),
+            _grow_operand("label_thin", f"{what}'s state", pair[1], (torch.uint8,), (H, W), slab.device))
 
 
 class LabelThin:
@@ -1850,17 +1781,14 @@ class LabelThin:
     `iterations` counts the marks, `voxels_deleted` what deleted() has seen so far."""
 
     def __init__(self, slab, z_base=0, block_voxels=None, info=None):
-        slab = _thin_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+        slab = _grow_operand("label_thin", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
         if slab.dim() != 3:
             raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
         D, H, W = (int(s) for s in slab.shape)
-        self.z_base = _thin_int("z_base", z_base, 0, 2 ** 62)
-        block_voxels = THIN_MAX_VOXELS if block_voxels is None else _thin_int("block_voxels", block_voxels, 1,
+        self.z_base = _label_int("label_thin", "z_base", z_base, 0, 2 ** 62)
+        block_voxels = THIN_MAX_VOXELS if block_voxels is None else _label_int("label_thin", "block_voxels", block_voxels, 1,
                                                                                THIN_MAX_VOXELS)
-        if H * W > block_voxels:
-            raise ValueError(f"label_thin: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                             f"{int(block_voxels)} voxels per call; there is no split within a slice")
-        per = max(1, block_voxels // max(H * W, 1))
+        per = _block_slices("label_thin", H, W, block_voxels)
         self.slab, self.iterations, self.voxels_deleted = slab, 0, 0
         self._stats = {} if info is None else info
         self._stats.update(blocks=-(-D // per), iterations=0, launches=0, active_tiles=0, work_bytes=slab.numel())
@@ -1871,14 +1799,13 @@ class LabelThin:
         require_gpu()
         item = slab.element_size()
         with torch.cuda.device(slab.device):
-            for z0 in range(0, D, per):
-                z1 = min(D, z0 + per)
+            for z0, z1, part, _, _ in _z_blocks(slab, None, None, per):
                 wb = query('emp_label_thin_work_bytes', z1 - z0, H, W)
                 if wb < 0:
                     raise ValueError(f"label_thin: {z1 - z0} x {H} x {W} voxels exceed the limit of {THIN_MAX_VOXELS} per call")
                 work = torch.empty((wb,), dtype=torch.uint8, device=slab.device)
                 self._stats['work_bytes'] += int(wb)
-                call('emp_label_thin_init', _ptr(slab[z0:z1]), item, z1 - z0, H, W, _ptr(self.state[z0:z1]), _ptr(work), wb,
+                call('emp_label_thin_init', _ptr(part), item, z1 - z0, H, W, _ptr(self.state[z0:z1]), _ptr(work), wb,
                      _current_stream(), alg_bytes=(z1 - z0) * H * W * (item + 1))
                 self._blocks.append(dict(z0=z0, z1=z1, work=work, listed=0))
             for b, c in zip(self._blocks, self._counters()):      # one sync: the lengths of the lists
@@ -1929,7 +1856,7 @@ class LabelThin:
 
     def run_pass(self, subfield, below=None, above=None):
         """step 2 for sub-field 0 .. 7"""
-        subfield = _thin_int("subfield", subfield, 0, 7)
+        subfield = _label_int("label_thin", "subfield", subfield, 0, 7)
         self._step('emp_label_thin_pass', below, above, subfield, lambda b, lo, hi: self.z_base + b['z0'])
 
     def deleted(self):
@@ -1958,7 +1885,7 @@ class LabelThin:
         else:
             if dtype is not None and dtype != out.dtype:
                 raise ValueError(f"label_thin: dtype={dtype} given together with an out of {out.dtype}")
-            _thin_operand("out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), slab.device)
+            _grow_operand("label_thin", "out", out, (torch.uint8, torch.int32, torch.uint32), tuple(slab.shape), slab.device)
         if out.element_size() == 1 and slab.element_size() == 4 and slab.numel():
             bits = slab.view(torch.int32)
             if int(bits.min()) < 0 or int(bits.max()) > 255:
@@ -1987,9 +1914,9 @@ def label_thin(slab, below=None, above=None, z_base=0, block_voxels=None, max_it
     'blocks', 'iterations', 'launches', 'voxels_deleted', 'active_tiles' (listed tiles) and 'work_bytes' (state
     included)."""
     if max_iterations is not None:
-        max_iterations = _thin_int("max_iterations", max_iterations, 1, 2 ** 62)
+        max_iterations = _label_int("label_thin", "max_iterations", max_iterations, 1, 2 ** 62)
     if below is not None or above is not None:                    # checked before anything is allocated
-        slab = _thin_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
+        slab = _grow_operand("label_thin", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
         if slab.dim() != 3:
             raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
         _thin_halo(slab, "below", below), _thin_halo(slab, "above", above)
@@ -2023,20 +1950,20 @@ def label_graph(skel, below=None, above=None, z_base=0, depth=None, block_voxels
     z-blocks with their true neighbour slices.  One host sync per block (the two totals).  info: a dict that receives
     'blocks', 'vertices', 'edges' and 'work_bytes' (largest workspace of one call)."""
     name = "label_graph"
-    skel = _mesh_operand(name, "skel", skel)
+    skel = _label_operand(name, "skel", skel)
     if skel.dim() != 3:
         raise ValueError(f"{name}: skel must be a (D, H, W) tensor, got {tuple(skel.shape)}")
     D, H, W = (int(s) for s in skel.shape)
     dev = skel.device
     if below is not None:
-        below = _mesh_operand(name, "below", below, skel.dtype, (H, W), dev)
+        below = _label_operand(name, "below", below, skel.dtype, (H, W), dev)
     if above is not None:
-        above = _mesh_operand(name, "above", above, skel.dtype, (H, W), dev)
-    z_base = _mesh_int(name, "z_base", z_base, 0)
-    depth = z_base + D if depth is None else _mesh_int(name, "depth", depth, z_base + D)
+        above = _label_operand(name, "above", above, skel.dtype, (H, W), dev)
+    z_base = _label_int(name, "z_base", z_base, 0)
+    depth = z_base + D if depth is None else _label_int(name, "depth", depth, z_base + D)
     if block_voxels is None:
         block_voxels = GRAPH_MAX_VOXELS
-    elif _mesh_int(name, "block_voxels", block_voxels, 1) > GRAPH_MAX_VOXELS:
+    elif _label_int(name, "block_voxels", block_voxels, 1) > GRAPH_MAX_VOXELS:
         raise ValueError(f"{name}: block_voxels must lie in 1 .. {GRAPH_MAX_VOXELS}, got {block_voxels!r}")
     stats = {} if info is None else info
     stats.update(blocks=0, vertices=0, edges=0, work_bytes=0)
@@ -2049,19 +1976,12 @@ def label_graph(skel, below=None, above=None, z_base=0, depth=None, block_voxels
     if depth * H * W > GRAPH_MAX_VOLUME:
         raise ValueError(f"{name}: a volume of {depth} x {H} x {W} = {depth * H * W} voxels is above the limit of 2^32 = "
                          f"{GRAPH_MAX_VOLUME} that the 32-bit voxel number of a key sets")
-    if H * W > block_voxels:
-        raise ValueError(f"{name}: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{int(block_voxels)} voxels per call; there is no split within a slice")
+    per = _block_slices(name, H, W, block_voxels)
     require_gpu()
     item = skel.element_size()
-    per = max(1, int(block_voxels) // (H * W))
     parts = [[], [], [], []]
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            part = skel[z0:z1]
-            lo = below if z0 == 0 else skel[z0 - 1]
-            hi = above if z1 == D else skel[z1]
+        for z0, z1, part, lo, hi in _z_blocks(skel, below, above, per):
             d = z1 - z0
             rows = d * H
             wb = query('emp_label_graph_count_work_bytes', rows)
@@ -2103,15 +2023,15 @@ def graph_finish(vertices, edges, shape, info=None):
         (vkeys, vdeg), (ekeys, ecodes) = vertices, edges
     except (TypeError, ValueError):
         raise ValueError(f"{name}: label_graph's pairs (vkeys, vdeg) and (ekeys, ecodes) expected") from None
-    vkeys = _mesh_operand(name, "vkeys", vkeys, torch.int64)
+    vkeys = _label_operand(name, "vkeys", vkeys, torch.int64)
     dev = vkeys.device
-    vdeg = _mesh_operand(name, "vdeg", vdeg, torch.int32, device=dev)
-    ekeys = _mesh_operand(name, "ekeys", ekeys, torch.int64, device=dev)
-    ecodes = _mesh_operand(name, "ecodes", ecodes, torch.int32, device=dev)
+    vdeg = _label_operand(name, "vdeg", vdeg, torch.int32, device=dev)
+    ekeys = _label_operand(name, "ekeys", ekeys, torch.int64, device=dev)
+    ecodes = _label_operand(name, "ecodes", ecodes, torch.int32, device=dev)
     if vkeys.dim() != 1 or vdeg.shape != vkeys.shape or ekeys.dim() != 1 or ecodes.shape != ekeys.shape:
         raise ValueError(f"{name}: vkeys and vdeg (nv,), ekeys and ecodes (ne,) expected, got {tuple(vkeys.shape)}, "
                          f"{tuple(vdeg.shape)}, {tuple(ekeys.shape)} and {tuple(ecodes.shape)}")
-    H, W = (_mesh_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
+    H, W = (_label_int(name, "shape", s, 1) for s in tuple(shape)[-2:])
     if H * W > GRAPH_MAX_VOLUME:
         raise ValueError(f"{name}: slices of {H} x {W} voxels hold more than 2^32 voxels")
     nv, ne = vkeys.numel(), ekeys.numel()
@@ -2185,7 +2105,7 @@ def _contacts_operand(what, t, dtype=None, shape=None):
 def _contacts_r2(r2, sampling):
     import math
     sampling = _morph_sampling('label_contacts', sampling)
-    r2 = _morph_bound('label_contacts', "r2", r2, 1, 2 ** 24 - 1)
+    r2 = _label_int('label_contacts', "r2", r2, 1, 2 ** 24 - 1)
     if r2 < min(sampling) ** 2:
         raise ValueError(f"label_contacts: r2 = {r2} is below the smallest squared pitch of {sampling}: the ball is a "
                          "point")
@@ -2241,17 +2161,14 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
     if block_voxels is None:
         block_voxels = CONTACTS_MAX_VOXELS
     else:
-        block_voxels = _morph_bound('label_contacts', "block_voxels", block_voxels, 1, MEASURE_MAX_VOXELS)
+        block_voxels = _label_int('label_contacts', "block_voxels", block_voxels, 1, MEASURE_MAX_VOXELS)
     stats = {} if info is None else info
     stats.update(blocks=0, tiles=0, records=0, work_bytes=0)
     empty = torch.zeros((0, CONTACT_COLUMNS), dtype=torch.int64, device=dev)
     if a.numel() == 0:
         return empty
-    if H * W > block_voxels:
-        raise ValueError(f"label_contacts: a single slice of {H} x {W} = {H * W} voxels exceeds the limit of "
-                         f"{block_voxels} voxels per call; there is no split within a slice")
+    per = _block_slices("label_contacts", H, W, block_voxels)
     require_gpu()
-    per = max(1, block_voxels // (H * W))
     n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
     bits = (lambda t: t.view(torch.int32)) if b.dtype == torch.uint32 else (lambda t: t)   # torch copies few uint32 tensors
 

@@ -99,7 +99,122 @@ __device__ __forceinline__ void uf_unite(int32_t *parent, int a, int b)
         a = old;
     }
 }
+
+// ------------------------------------------------------------------------------------------ labelled-volume stages
+// The labels of the voxels x .. x + 3 of a row as uint32, and the mask of those inside the row.  One aligned load (16
+// bytes of uint32, 4 bytes of uint8) where the group lies inside the row on such an address, voxel by voxel otherwise:
+// the narrow path, same values.  Positions outside the row read as 0.
+template <typename T>
+__device__ __forceinline__ uint32_t emp_load4(const T *__restrict__ src, int64_t x, int64_t W, uint32_t *v)
+{
+    if (x >= 0 && x + 4 <= W && (reinterpret_cast<uintptr_t>(src + x) & (uintptr_t)(4 * sizeof(T) - 1)) == 0) {
+        if constexpr (sizeof(T) == 4) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(src + x);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+            const uint32_t q = *reinterpret_cast<const uint32_t *>(src + x);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (q >> (8 * j)) & 0xffu;
+        }
+        return 0xfu;
+    }
+    uint32_t ok = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool in = x + j >= 0 && x + j < W;
+        v[j] = in ? (uint32_t)src[x + j] : 0u;
+        ok |= (uint32_t)in << j;
+    }
+    return ok;
+}
+// the same for a row that may be missing: a null row reads as 0
+template <typename T>
+__device__ __forceinline__ void emp_fetch4(const T *__restrict__ src, int64_t x, int64_t W, uint32_t *v)
+{
+    if (src == nullptr) v[0] = v[1] = v[2] = v[3] = 0u;
+    else emp_load4<T>(src, x, W, v);
+}
+
+template <typename T> __global__ void emp_zero_kernel(T *__restrict__ v, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        v[i] = 0;
+}
+
+// head[i] = 1 where sorted key i opens a run of keys that are equal above bit SHIFT (0: the whole key; 32: the label
+// in the high half)
+template <int SHIFT>
+__global__ void emp_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        head[i] = (i == 0 || (keys[i - 1] >> SHIFT) != (keys[i] >> SHIFT)) ? 1 : 0;
+}
+
+// first index in [lo, hi) whose label (the high half of the key) is >= label (UPPER: > label)
+template <bool UPPER>
+__device__ __forceinline__ int64_t emp_label_bound(const uint64_t *__restrict__ keys, int64_t lo, int64_t hi, uint64_t label)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t l = keys[mid] >> 32;
+        if (UPPER ? l <= label : l < label) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
 #endif
+
+// What the entry points that take a label volume (lab, item, D, H, W) ask of it before their own voxel limit and
+// alignment; an entry point whose `lab` may be null (D == 0) or is tested later uses EMP_REQUIRE_VOLUME alone.
+#define EMP_REQUIRE_VOLUME(what)                                                                                     \
+    do {                                                                                                             \
+        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);    \
+        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,       \
+                    (long long)H, (long long)W);                                                                     \
+    } while (0)
+#define EMP_REQUIRE_LABELS(what)                                                                                     \
+    do {                                                                                                             \
+        EMP_REQUIRE(lab, what ": null pointer");                                                                     \
+        EMP_REQUIRE_VOLUME(what);                                                                                    \
+    } while (0)
+
+// The workspace of a "count the rows, then scan" step over R rows: the row counts and the scan's scratch.
+struct EmpCountWork {
+    int32_t *counts, *scantmp;
+    int64_t total;
+};
+static inline EmpCountWork emp_count_carve(void *work, int64_t R)
+{
+    if (R < 1) R = 1;
+    EmpCarver c(work);
+    EmpCountWork L;
+    L.counts = c.take<int32_t>(R);
+    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R));
+    L.total = c.bytes();
+    return L;
+}
+
+// The grid of 8 x 8 x 64 tiles over a slab that the sweeping stages (emp_label_grow.hip, emp_label_thin.hip) work by;
+// a slab they accept has at most 2^31 - 1 voxels.
+#define EMP_TILE_Z 8
+#define EMP_TILE_Y 8
+#define EMP_TILE_X 64
+struct EmpTiles {
+    int64_t nz, ny, nx, n;
+};
+static inline EmpTiles emp_tiles(int64_t D, int64_t H, int64_t W)
+{
+    EmpTiles t;
+    t.nz = emp_cdiv(D, EMP_TILE_Z);
+    t.ny = emp_cdiv(H, EMP_TILE_Y);
+    t.nx = emp_cdiv(W, EMP_TILE_X);
+    t.n = t.nz * t.ny * t.nx;
+    return t;
+}
+static inline bool emp_tiles_shape_ok(int64_t D, int64_t H, int64_t W)
+{
+    return D >= 0 && H > 0 && W > 0 && H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D);
+}
 
 // emp_measure.hip: the run extraction of its rows kernel without the neighbour rows (see there)
 int emp_label_rows_extract(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,

@@ -139,10 +139,7 @@ __global__ void cc_stats_kernel(int64_t n, int64_t H, int64_t z_base, const int3
 // same shape checks as emp_measure.hip: one run per voxel is the worst case and the scan is int32
 #define CC_REQUIRE_SHAPE(what)                                                                                       \
     do {                                                                                                             \
-        EMP_REQUIRE(lab, what ": null pointer");                                                                     \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);    \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,       \
-                    (long long)H, (long long)W);                                                                     \
+        EMP_REQUIRE_LABELS(what);                                                                                    \
         EMP_REQUIRE(H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D),                                  \
                     what ": %lld x %lld x %lld voxels could hold more than 2^31 - 1 runs; cut the slab into z-blocks", \
                     (long long)D, (long long)H, (long long)W);                                                       \

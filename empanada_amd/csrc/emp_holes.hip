@@ -110,12 +110,6 @@ __global__ __launch_bounds__(256) void hl_rows_kernel(const T *__restrict__ lab,
     }
 }
 
-__global__ void hl_zero_kernel(int32_t *__restrict__ v, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        v[i] = 0;
-}
-
 // pos[root] numbers the roots in run order; the root's own thread starts the component's row
 __global__ void hl_comp_kernel(int64_t n, int64_t W, int64_t first_base, const int32_t *__restrict__ parent,
                                const int32_t *__restrict__ flag, const int32_t *__restrict__ pos,
@@ -287,10 +281,7 @@ __global__ __launch_bounds__(256) void hl_survey_kernel(int64_t n, int64_t D, in
 // same shape checks as emp_measure.hip: one run per voxel is the worst case and the scan is int32
 #define HL_REQUIRE_SHAPE(what)                                                                                       \
     do {                                                                                                             \
-        EMP_REQUIRE(lab, what ": null pointer");                                                                     \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);    \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,       \
-                    (long long)H, (long long)W);                                                                     \
+        EMP_REQUIRE_LABELS(what);                                                                                    \
         EMP_REQUIRE(H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D),                                  \
                     what ": %lld x %lld x %lld voxels could hold more than 2^31 - 1 runs; cut the slab into z-blocks", \
                     (long long)D, (long long)H, (long long)W);                                                       \
@@ -298,21 +289,7 @@ __global__ __launch_bounds__(256) void hl_survey_kernel(int64_t n, int64_t D, in
     } while (0)
 
 // ------------------------------------------------------------------------------------------ count + scan
-struct HlCountWork {
-    int32_t *counts, *scantmp;
-    int64_t total;
-};
-static HlCountWork hl_count_carve(void *work, int64_t R)
-{
-    if (R < 1) R = 1;
-    EmpCarver c(work);
-    HlCountWork L;
-    L.counts = c.take<int32_t>(R);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R));
-    L.total = c.bytes();
-    return L;
-}
-extern "C" int64_t emp_label_holes_count_work_bytes(int64_t R) { return hl_count_carve(nullptr, R).total; }
+extern "C" int64_t emp_label_holes_count_work_bytes(int64_t R) { return emp_count_carve(nullptr, R).total; }
 
 template <typename T, bool EXTRACT>
 static int hl_launch_rows(const void *lab, int64_t n_rows, int64_t W, int32_t *row_counts, const int32_t *row_offsets,
@@ -329,12 +306,12 @@ extern "C" int emp_label_holes_count(const void *lab, int item, int64_t D, int64
     HL_REQUIRE_SHAPE("label_holes_count");
     EMP_REQUIRE(work && row_offsets, "label_holes_count: null pointer");
     const int64_t R = D * H;
-    HlCountWork C = hl_count_carve(work, R);
+    EmpCountWork C = emp_count_carve(work, R);
     EMP_REQUIRE(work_bytes >= C.total, "label_holes_count: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)C.total);
     hipStream_t st = emp_stream(stream);
     if (R == 0) {
-        EMP_LAUNCH(hl_zero_kernel, 1, 64, st, row_offsets, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
         return EMP_OK;
     }
     const CcWork none = {};
@@ -362,7 +339,7 @@ extern "C" int emp_label_holes(const void *lab, int item, int64_t D, int64_t H, 
                 (long long)n_runs, (long long)(D * H * W));
     hipStream_t st = emp_stream(stream);
     if (n_runs == 0) {
-        EMP_LAUNCH(hl_zero_kernel, 1, 64, st, n_out, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, n_out, (int64_t)1);
         return EMP_OK;
     }
     EMP_REQUIRE(work && out_table, "label_holes: null pointer");
@@ -371,7 +348,7 @@ extern "C" int emp_label_holes(const void *lab, int item, int64_t D, int64_t H, 
                 (long long)L.total);
     // every run's value is 0, which is what the paint step compares a lut entry with; a slot that the extraction does
     // not reach (labels changed since step 1) reads as an empty run of row 0
-    EMP_LAUNCH(hl_zero_kernel, emp_grid(L.keep / 4, 256, 4096), 256, st, L.row, L.keep / 4);
+    EMP_LAUNCH(emp_zero_kernel<int32_t>, emp_grid(L.keep / 4, 256, 4096), 256, st, L.row, L.keep / 4);
     int rc = item == 4 ? hl_launch_rows<uint32_t, true>(lab, D * H, W, nullptr, row_offsets, n_runs, L, st)
                        : hl_launch_rows<uint8_t, true>(lab, D * H, W, nullptr, row_offsets, n_runs, L, st);
     if (rc != EMP_OK) return rc;

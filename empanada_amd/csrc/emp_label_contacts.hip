@@ -479,12 +479,6 @@ extern "C" int emp_label_contacts_emit(const void *a, int item_a, const void *b,
 }
 
 // ------------------------------------------------------------------------------------------ rows of the sorted records
-__global__ void lc_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || keys[i - 1] != keys[i]) ? 1 : 0;
-}
-
 __global__ void lc_rows_init_kernel(const uint64_t *__restrict__ keys, const int32_t *__restrict__ head,
                                     const int32_t *__restrict__ pos, int64_t n, int64_t *__restrict__ table,
                                     int64_t n_rows)
@@ -592,7 +586,7 @@ extern "C" int emp_label_contacts_rows(const uint64_t *keys, int64_t n, void *wo
     LcRowsWork L = lc_rows_carve(work, n);
     EMP_REQUIRE(work_bytes >= L.bytes, "label_contacts_rows: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.bytes);
-    EMP_LAUNCH(lc_heads_kernel, emp_grid(n, 256, 4096), 256, st, keys, n, L.head);
+    EMP_LAUNCH(emp_heads_kernel<0>, emp_grid(n, 256, 4096), 256, st, keys, n, L.head);
     int rc = emp_exclusive_scan_i32(L.head, n, L.pos, L.scantmp, stream);
     if (rc != EMP_OK) return rc;
     if (hipMemcpyAsync(n_rows, L.pos + n, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)

@@ -22,9 +22,9 @@
 // initialisation and the counter of blocks that stored something.  No block waits on another.
 #include "emp_common.h"
 
-#define LG_TZ 8
-#define LG_TY 8
-#define LG_TX 64
+#define LG_TZ EMP_TILE_Z
+#define LG_TY EMP_TILE_Y
+#define LG_TX EMP_TILE_X
 #define LG_PZ (LG_TZ + 2)
 #define LG_PY (LG_TY + 2)
 #define LG_PX (LG_TX + 2)
@@ -37,19 +37,6 @@
 #define LG_STEP (1ULL << 32)
 
 typedef unsigned long long lg_key;
-
-struct LgTiles {
-    int64_t nz, ny, nx, n;
-};
-static LgTiles lg_tiles(int64_t D, int64_t H, int64_t W)
-{
-    LgTiles t;
-    t.nz = emp_cdiv(D, LG_TZ);
-    t.ny = emp_cdiv(H, LG_TY);
-    t.nx = emp_cdiv(W, LG_TX);
-    t.n = t.nz * t.ny * t.nx;
-    return t;
-}
 
 // counters[0]: length of the list; counters[1 + slot]: blocks that stored something in the sweeps given that slot
 struct LgWork {
@@ -71,15 +58,10 @@ static LgWork lg_carve(void *work, int64_t n_tiles)
     return L;
 }
 
-static bool lg_shape_ok(int64_t D, int64_t H, int64_t W)
-{
-    return D >= 0 && H > 0 && W > 0 && H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D);
-}
-
 extern "C" int64_t emp_label_grow_work_bytes(int64_t D, int64_t H, int64_t W)
 {
-    if (!lg_shape_ok(D, H, W)) return -1;
-    return lg_carve(nullptr, lg_tiles(D, H, W).n).total;
+    if (!emp_tiles_shape_ok(D, H, W)) return -1;
+    return lg_carve(nullptr, emp_tiles(D, H, W).n).total;
 }
 
 __global__ void lg_clear_kernel(int64_t n_tiles, lg_key *__restrict__ counters, uint8_t *__restrict__ due0,
@@ -97,7 +79,7 @@ __device__ __forceinline__ int lg_face_bits(int lz, int ly, int lx)
            (lx == 0 ? 32 : 0) | (lx == LG_TX - 1 ? 64 : 0);
 }
 
-__device__ __forceinline__ void lg_mark(int bits, int64_t tz, int64_t ty, int64_t tx, LgTiles T, int64_t tile,
+__device__ __forceinline__ void lg_mark(int bits, int64_t tz, int64_t ty, int64_t tx, EmpTiles T, int64_t tile,
                                         uint8_t *due)
 {
     if (bits & 1) due[tile] = 1;
@@ -111,7 +93,7 @@ __device__ __forceinline__ void lg_mark(int bits, int64_t tz, int64_t ty, int64_
 
 template <typename T>
 __global__ __launch_bounds__(LG_THREADS) void lg_init_kernel(const T *__restrict__ lab, const uint32_t *__restrict__ seeds,
-                                                             int64_t D, int64_t H, int64_t W, LgTiles tiles,
+                                                             int64_t D, int64_t H, int64_t W, EmpTiles tiles,
                                                              lg_key *__restrict__ state, lg_key *counters,
                                                              int32_t *__restrict__ list, uint8_t *due)
 {
@@ -150,11 +132,10 @@ __global__ __launch_bounds__(LG_THREADS) void lg_init_kernel(const T *__restrict
 
 #define LG_REQUIRE_SHAPE(what)                                                                                         \
     do {                                                                                                               \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);      \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,         \
-                    (long long)H, (long long)W);                                                                       \
-        EMP_REQUIRE(lg_shape_ok(D, H, W), what ": %lld x %lld x %lld voxels are more than 2^31 - 1; cut the slab into " \
-                    "z-blocks", (long long)D, (long long)H, (long long)W);                                             \
+        EMP_REQUIRE_VOLUME(what);                                                                                      \
+        EMP_REQUIRE(emp_tiles_shape_ok(D, H, W),                                                                       \
+                    what ": %lld x %lld x %lld voxels are more than 2^31 - 1; cut the slab into z-blocks",             \
+                    (long long)D, (long long)H, (long long)W);                                                         \
     } while (0)
 
 extern "C" int emp_label_grow_init(const void *lab, int item, const uint32_t *seeds, int64_t D, int64_t H, int64_t W,
@@ -162,7 +143,7 @@ extern "C" int emp_label_grow_init(const void *lab, int item, const uint32_t *se
 {
     LG_REQUIRE_SHAPE("label_grow_init");
     EMP_REQUIRE(work, "label_grow_init: null pointer");
-    const LgTiles T = lg_tiles(D, H, W);
+    const EmpTiles T = emp_tiles(D, H, W);
     LgWork L = lg_carve(work, T.n);
     EMP_REQUIRE(work_bytes >= L.total, "label_grow_init: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.total);
@@ -204,7 +185,7 @@ __device__ __forceinline__ lg_key lg_next(lg_key c)
 
 template <typename T>
 __global__ __launch_bounds__(LG_THREADS) void lg_sweep_kernel(const T *__restrict__ lab, int64_t D, int64_t H, int64_t W,
-                                                              LgTiles tiles, LgHalo<T> halo, lg_key *state,
+                                                              EmpTiles tiles, LgHalo<T> halo, lg_key *state,
                                                               const int32_t *__restrict__ list, uint8_t *due_now,
                                                               uint8_t *due_next, int force, lg_key *counter)
 {
@@ -332,7 +313,7 @@ extern "C" int emp_label_grow_sweep(const void *lab, int item, int64_t D, int64_
     EMP_REQUIRE((turn == 0 || turn == 1) && force >= 0 && force <= 3 && slot >= 0 && slot < LG_SLOTS,
                 "label_grow_sweep: turn = %d, force = %d, slot = %d outside 0 .. 1, 0 .. 3, 0 .. %d", turn, force, slot,
                 LG_SLOTS - 1);
-    const LgTiles T = lg_tiles(D, H, W);
+    const EmpTiles T = emp_tiles(D, H, W);
     EMP_REQUIRE(n_listed >= 0 && n_listed <= T.n, "label_grow_sweep: %lld listed tiles, the slab has %lld",
                 (long long)n_listed, (long long)T.n);
     if (D == 0 || n_listed == 0) return EMP_OK;

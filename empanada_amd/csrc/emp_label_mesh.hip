@@ -15,31 +15,6 @@
 // inside its object's own range of the keys.  Smoothing gathers over a six-slot neighbour table.
 #include "emp_common.h"
 
-// the four positions x .. x + 3 of a row as uint32: one aligned load (16 bytes of uint32, 4 of uint8) where the group
-// lies inside the row on such an address, voxel by voxel otherwise: the same values.  A null row and positions outside
-// the row read as 0.
-template <typename T>
-__device__ __forceinline__ void lm_fetch(const T *__restrict__ src, int64_t x, int64_t W, uint32_t *v)
-{
-    if (src == nullptr) {
-        v[0] = v[1] = v[2] = v[3] = 0u;
-        return;
-    }
-    if (x >= 0 && x + 4 <= W && (reinterpret_cast<uintptr_t>(src + x) & (uintptr_t)(4 * sizeof(T) - 1)) == 0) {
-        if constexpr (sizeof(T) == 4) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(src + x);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-            const uint32_t q = *reinterpret_cast<const uint32_t *>(src + x);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (q >> (8 * j)) & 0xffu;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (x + j >= 0 && x + j < W) ? (uint32_t)src[x + j] : 0u;
-}
-
 template <typename T>
 __device__ __forceinline__ uint32_t lm_one(const T *__restrict__ src, int64_t x, int64_t W)
 {
@@ -115,16 +90,16 @@ __global__ __launch_bounds__(256) void lm_rows_kernel(const T *__restrict__ lab,
             for (int64_t x0 = -shift; x0 < W; x0 += 256) {
                 const int64_t x = x0 + (int64_t)lane * 4;
                 uint32_t c[4];
-                lm_fetch<T>(src, x, W, c);
+                emp_fetch4<T>(src, x, W, c);
                 const bool any = (c[0] | c[1] | c[2] | c[3]) != 0u;
                 if (__ballot(any) == 0ull) continue;                            // background alone owns no quad
                 // only a lane that holds a non-zero voxel reads the neighbour rows
                 uint32_t a[4] = {0u, 0u, 0u, 0u}, b[4] = {0u, 0u, 0u, 0u}, f[4] = {0u, 0u, 0u, 0u}, g[4] = {0u, 0u, 0u, 0u};
                 if (any) {
-                    lm_fetch<T>(ym, x, W, a);
-                    lm_fetch<T>(yp, x, W, b);
-                    lm_fetch<T>(zm, x, W, f);
-                    lm_fetch<T>(zp, x, W, g);
+                    emp_fetch4<T>(ym, x, W, a);
+                    emp_fetch4<T>(yp, x, W, b);
+                    emp_fetch4<T>(zm, x, W, f);
+                    emp_fetch4<T>(zp, x, W, g);
                 }
                 uint32_t left = __shfl_up(c[3], 1), right = __shfl_down(c[0], 1);
                 if (lane == 0) left = lm_one<T>(src, x - 1, W);
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(256) void lm_rows_kernel(const T *__restrict__ lab,
                     uint32_t any = 0u;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        lm_fetch<T>(r[k], x, W, &q[k][1]);
+                        emp_fetch4<T>(r[k], x, W, &q[k][1]);
                         q[k][0] = __shfl_up(q[k][4], 1);
                         if (lane == 0) q[k][0] = lm_one<T>(r[k], x - 1, W);
                         any |= q[k][0] | q[k][1] | q[k][2] | q[k][3] | q[k][4];
@@ -227,10 +202,7 @@ __global__ __launch_bounds__(256) void lm_rows_kernel(const T *__restrict__ lab,
 #define LM_MAX_VOXELS (1LL << 26)
 #define LM_REQUIRE_SHAPE(what)                                                                                        \
     do {                                                                                                              \
-        EMP_REQUIRE(lab, what ": null pointer");                                                                      \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);     \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,        \
-                    (long long)H, (long long)W);                                                                      \
+        EMP_REQUIRE_LABELS(what);                                                                                     \
         EMP_REQUIRE(H <= LM_MAX_VOXELS / W && (D == 0 || H * W <= LM_MAX_VOXELS / D),                                 \
                     what ": %lld x %lld x %lld voxels exceed 2^26 per call; cut the slab into z-blocks",              \
                     (long long)D, (long long)H, (long long)W);                                                        \
@@ -243,21 +215,7 @@ __global__ __launch_bounds__(256) void lm_rows_kernel(const T *__restrict__ lab,
 
 static int64_t lm_rows(int64_t D, int64_t H, int top) { return D * H + (D + (top ? 1 : 0)) * (H + 1); }
 
-struct LmCountWork {
-    int32_t *counts, *scantmp;
-    int64_t total;
-};
-static LmCountWork lm_count_carve(void *work, int64_t R)
-{
-    if (R < 1) R = 1;
-    EmpCarver c(work);
-    LmCountWork L;
-    L.counts = c.take<int32_t>(R);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R));
-    L.total = c.bytes();
-    return L;
-}
-extern "C" int64_t emp_label_mesh_count_work_bytes(int64_t R) { return lm_count_carve(nullptr, R).total; }
+extern "C" int64_t emp_label_mesh_count_work_bytes(int64_t R) { return emp_count_carve(nullptr, R).total; }
 
 template <typename T, bool EMIT>
 static int lm_launch(const void *lab, int64_t D, int64_t H, int64_t W, const void *below, const void *above, int top,
@@ -269,12 +227,6 @@ static int lm_launch(const void *lab, int64_t D, int64_t H, int64_t W, const voi
     return EMP_OK;
 }
 
-__global__ void lm_zero_kernel(int32_t *__restrict__ v, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        v[i] = 0;
-}
-
 extern "C" int emp_label_mesh_count(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below,
                                     const void *above, int top, void *work, int64_t work_bytes, int32_t *row_offsets,
                                     void *stream)
@@ -282,12 +234,12 @@ extern "C" int emp_label_mesh_count(const void *lab, int item, int64_t D, int64_
     LM_REQUIRE_SHAPE("label_mesh_count");
     EMP_REQUIRE(work && row_offsets, "label_mesh_count: null pointer");
     const int64_t R = lm_rows(D, H, top);
-    LmCountWork L = lm_count_carve(work, R);
+    EmpCountWork L = emp_count_carve(work, R);
     EMP_REQUIRE(work_bytes >= L.total, "label_mesh_count: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.total);
     hipStream_t st = emp_stream(stream);
     if (R == 0) {
-        EMP_LAUNCH(lm_zero_kernel, 1, 64, st, row_offsets, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
         return EMP_OK;
     }
     const LmOut none = {};
@@ -326,25 +278,6 @@ extern "C" int emp_label_mesh_emit(const void *lab, int item, int64_t D, int64_t
 // ------------------------------------------------------------------------------------------ index
 #define LM_OBJ_COLS 5
 
-__global__ void lm_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || (keys[i - 1] >> 32) != (keys[i] >> 32)) ? 1 : 0;
-}
-
-// first index in [lo, hi) whose label (the high half) is >= label (UPPER: > label)
-template <bool UPPER>
-__device__ __forceinline__ int64_t lm_label_bound(const uint64_t *__restrict__ keys, int64_t lo, int64_t hi, uint64_t label)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t l = keys[mid] >> 32;
-        if (UPPER ? l <= label : l < label) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // Every sorted key becomes a vertex (z, y, x); the first key of a label opens the label's row of the objects table --
 // label, v_begin, q_begin, q_end -- and closes the row before it (v_end).  Different rows, different slots: plain stores.
 __global__ void lm_objects_kernel(const uint64_t *__restrict__ vkeys, int64_t nv, const int32_t *__restrict__ head,
@@ -366,8 +299,8 @@ __global__ void lm_objects_kernel(const uint64_t *__restrict__ vkeys, int64_t nv
                 int64_t *o = objects + row * LM_OBJ_COLS;
                 o[0] = (int64_t)label;
                 o[1] = i;
-                o[3] = lm_label_bound<false>(qkeys, 0, nq, label);
-                o[4] = lm_label_bound<true>(qkeys, 0, nq, label);
+                o[3] = emp_label_bound<false>(qkeys, 0, nq, label);
+                o[4] = emp_label_bound<true>(qkeys, 0, nq, label);
             }
             if (row > 0 && row - 1 < max_objects) objects[(row - 1) * LM_OBJ_COLS + 2] = i;
         }
@@ -452,7 +385,7 @@ extern "C" int emp_label_mesh_index(const uint64_t *vkeys, int64_t nv, const uin
     hipStream_t st = emp_stream(stream);
     if (nv == 0) {
         // no vertex: no quad can be resolved
-        EMP_LAUNCH(lm_zero_kernel, 1, 64, st, n_objects, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, n_objects, (int64_t)1);
         if (nq > 0) {
             EMP_REQUIRE(quads, "label_mesh_index: null pointer");
             if (hipMemsetAsync(quads, 0xff, (size_t)nq * 4 * sizeof(int32_t), st) != hipSuccess)
@@ -469,7 +402,7 @@ extern "C" int emp_label_mesh_index(const uint64_t *vkeys, int64_t nv, const uin
     int rc = emp_compact(
         L.head, nv, L.pos, L.scantmp, n_objects, stream, "label_mesh_index: count copy",
         [&]() -> int {
-            EMP_LAUNCH(lm_heads_kernel, grid, 256, st, vkeys, nv, L.head);
+            EMP_LAUNCH(emp_heads_kernel<32>, grid, 256, st, vkeys, nv, L.head);
             return EMP_OK;
         },
         [&]() -> int {

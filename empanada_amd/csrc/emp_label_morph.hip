@@ -33,34 +33,6 @@ template <typename T> struct MoVol {
     }
 };
 
-// labels of the voxels x .. x + 3 of a row and the mask of those inside it.  One aligned load (16 bytes of uint32, 4 of
-// uint8) where the group lies inside the row on such an address, voxel by voxel otherwise: the same values.
-template <typename T>
-__device__ __forceinline__ uint32_t mo_load4(const T *__restrict__ src, int64_t x, int64_t W, uint32_t v[4])
-{
-    if (x >= 0 && x + 4 <= W && (reinterpret_cast<uintptr_t>(src + x) & (uintptr_t)(4 * sizeof(T) - 1)) == 0) {
-        if constexpr (sizeof(T) == 4) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(src + x);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-            const uint32_t q = *reinterpret_cast<const uint32_t *>(src + x);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (q >> (8 * j)) & 0xffu;
-        }
-        return 0xfu;
-    }
-    uint32_t ok = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[j] = 0u;
-        if (x + j >= 0 && x + j < W) {
-            v[j] = (uint32_t)src[x + j];
-            ok |= 1u << j;
-        }
-    }
-    return ok;
-}
-
 // ------------------------------------------------------------------------------------------ distance: x pass
 // f[row][x] = min(cap, w k^2), k = steps to the nearest voxel of the row with another label (none on a side whose run
 // reaches the row's end), 0 on zero voxels.  The forward sweep leaves the steps to the left in f, clamped to MO_FAR, and
@@ -83,7 +55,7 @@ __global__ __launch_bounds__(256) void mo_edt_rows_kernel(MoVol<T> vol, int64_t 
         int carry_pos = -1;
         for (int64_t x0 = -shift; x0 < W; x0 += 256) {
             const int64_t x = x0 + (int64_t)lane * 4;
-            const uint32_t ok = mo_load4<T>(src, x, W, v);
+            const uint32_t ok = emp_load4<T>(src, x, W, v);
             uint32_t pv = __shfl_up(v[3], 1);
             if (lane == 0) pv = carry_lab;
             int s[4], run = -1;
@@ -118,7 +90,7 @@ __global__ __launch_bounds__(256) void mo_edt_rows_kernel(MoVol<T> vol, int64_t 
         carry_pos = none;
         for (int64_t x0 = last; x0 >= -shift; x0 -= 256) {
             const int64_t x = x0 + (int64_t)lane * 4;
-            const uint32_t ok = mo_load4<T>(src, x, W, v);
+            const uint32_t ok = emp_load4<T>(src, x, W, v);
             uint32_t nv = __shfl_down(v[0], 1);
             if (lane == 63) nv = carry_lab;
             int e[4], run = none;
@@ -324,9 +296,7 @@ struct MoShape {
 
 #define MO_REQUIRE_ARGS(what)                                                                                         \
     do {                                                                                                              \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);     \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,        \
-                    (long long)H, (long long)W);                                                                      \
+        EMP_REQUIRE_VOLUME(what);                                                                                     \
         EMP_REQUIRE(hb >= 0 && ha >= 0, what ": bad halo counts (%lld, %lld)", (long long)hb, (long long)ha);         \
         EMP_REQUIRE(D <= 0x7fffffffLL && hb <= 0x7fffffffLL && ha <= 0x7fffffffLL && H <= 0x7fffffffLL / W &&        \
                         (D + hb + ha == 0 || H * W <= 0x7fffffffLL / (D + hb + ha)),                                  \

@@ -28,9 +28,9 @@
 // Nothing is atomic in global memory but the list's length in the initialisation and the counter of deleted voxels.
 #include "emp_common.h"
 
-#define LT_TZ 8
-#define LT_TY 8
-#define LT_TX 64
+#define LT_TZ EMP_TILE_Z
+#define LT_TY EMP_TILE_Y
+#define LT_TX EMP_TILE_X
 #define LT_PZ (LT_TZ + 2)
 #define LT_PY (LT_TY + 2)
 #define LT_PX (LT_TX + 2)
@@ -132,19 +132,6 @@ extern "C" int emp_skel_classify(const uint32_t *masks, int64_t n, uint8_t *out,
 }
 
 // ------------------------------------------------------------------------------------------ tiles and workspace
-struct LtTiles {
-    int64_t nz, ny, nx, n;
-};
-static LtTiles lt_tiles(int64_t D, int64_t H, int64_t W)
-{
-    LtTiles t;
-    t.nz = emp_cdiv(D, LT_TZ);
-    t.ny = emp_cdiv(H, LT_TY);
-    t.nx = emp_cdiv(W, LT_TX);
-    t.n = t.nz * t.ny * t.nx;
-    return t;
-}
-
 // counters[0]: length of the list; counters[1]: voxels deleted since the initialisation.  The layout is part of the
 // interface (include/emp_hip.h, E8): tools read the due flags.
 struct LtWork {
@@ -166,28 +153,22 @@ static LtWork lt_carve(void *work, int64_t n_tiles)
     return L;
 }
 
-static bool lt_shape_ok(int64_t D, int64_t H, int64_t W)
-{
-    return D >= 0 && H > 0 && W > 0 && H <= LT_MAX_VOXELS / W && (D == 0 || H * W <= LT_MAX_VOXELS / D);
-}
-
 extern "C" int64_t emp_label_thin_work_bytes(int64_t D, int64_t H, int64_t W)
 {
-    if (!lt_shape_ok(D, H, W)) return -1;
-    return lt_carve(nullptr, lt_tiles(D, H, W).n).total;
+    if (!emp_tiles_shape_ok(D, H, W)) return -1;
+    return lt_carve(nullptr, emp_tiles(D, H, W).n).total;
 }
 
 #define LT_REQUIRE_SHAPE(what)                                                                                         \
     do {                                                                                                               \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);      \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,         \
-                    (long long)H, (long long)W);                                                                       \
-        EMP_REQUIRE(lt_shape_ok(D, H, W), what ": %lld x %lld x %lld voxels are more than 2^31 - 1; cut the slab into " \
-                    "z-blocks", (long long)D, (long long)H, (long long)W);                                             \
+        EMP_REQUIRE_VOLUME(what);                                                                                      \
+        EMP_REQUIRE(emp_tiles_shape_ok(D, H, W),                                                                       \
+                    what ": %lld x %lld x %lld voxels are more than 2^31 - 1; cut the slab into z-blocks",             \
+                    (long long)D, (long long)H, (long long)W);                                                         \
     } while (0)
 
 #define LT_REQUIRE_WORK(what)                                                                                          \
-    const LtTiles T = lt_tiles(D, H, W);                                                                               \
+    const EmpTiles T = emp_tiles(D, H, W);                                                                             \
     LtWork L = lt_carve(work, T.n);                                                                                    \
     EMP_REQUIRE(work, what ": null pointer");                                                                          \
     EMP_REQUIRE(work_bytes >= L.total, what ": workspace too small (%lld < %lld)", (long long)work_bytes,              \
@@ -215,7 +196,7 @@ __global__ void lt_clear_kernel(int64_t n_tiles, lt_u64 *__restrict__ counters, 
 // ------------------------------------------------------------------------------------------ init
 template <typename T>
 __global__ __launch_bounds__(LT_THREADS) void lt_init_kernel(const T *__restrict__ lab, int64_t D, int64_t H, int64_t W,
-                                                             LtTiles tiles, uint8_t *__restrict__ state,
+                                                             EmpTiles tiles, uint8_t *__restrict__ state,
                                                              lt_u64 *counters, int32_t *__restrict__ list,
                                                              uint8_t *__restrict__ due_mark)
 {
@@ -291,7 +272,7 @@ __device__ __forceinline__ uint32_t lt_object(const T *__restrict__ lab, const u
 // passes iff it then holds an alive, marked, not-kept voxel.  Only bit 2 of the tile's own bytes changes.
 template <typename T>
 __global__ __launch_bounds__(LT_THREADS) void lt_mark_kernel(const T *__restrict__ lab, int64_t D, int64_t H, int64_t W,
-                                                             LtTiles tiles, LtHalo<T> halo, uint8_t *state,
+                                                             EmpTiles tiles, LtHalo<T> halo, uint8_t *state,
                                                              const int32_t *__restrict__ list, uint8_t *due_mark,
                                                              uint8_t *due_pass, int force)
 {
@@ -329,7 +310,7 @@ __global__ __launch_bounds__(LT_THREADS) void lt_mark_kernel(const T *__restrict
 // Step 2 for one sub-field.  pz: the parity of the LOCAL z of the sub-field's voxels (the caller folds z_base in).
 template <typename T>
 __global__ __launch_bounds__(LT_THREADS) void lt_pass_kernel(const T *__restrict__ lab, int64_t D, int64_t H, int64_t W,
-                                                             LtTiles tiles, LtHalo<T> halo, uint8_t *state,
+                                                             EmpTiles tiles, LtHalo<T> halo, uint8_t *state,
                                                              const int32_t *__restrict__ list, uint8_t *due_mark,
                                                              uint8_t *due_pass, int pz, int py, int px,
                                                              lt_u64 *counter)
@@ -417,8 +398,8 @@ extern "C" int emp_label_thin_mark(LT_SWEEP_ARGS, int force, void *stream)
     LT_REQUIRE_SHAPE("label_thin_mark");
     LT_REQUIRE_HALO("label_thin_mark");
     EMP_REQUIRE(force >= 0 && force <= 3, "label_thin_mark: force = %d outside 0 .. 3", force);
-    EMP_REQUIRE(n_listed >= 0 && n_listed <= lt_tiles(D, H, W).n, "label_thin_mark: %lld listed tiles, the slab has %lld",
-                (long long)n_listed, (long long)lt_tiles(D, H, W).n);
+    EMP_REQUIRE(n_listed >= 0 && n_listed <= emp_tiles(D, H, W).n, "label_thin_mark: %lld listed tiles, the slab has %lld",
+                (long long)n_listed, (long long)emp_tiles(D, H, W).n);
     if (D == 0 || n_listed == 0) return EMP_OK;
     EMP_REQUIRE(lab && state, "label_thin_mark: null pointer");
     LT_REQUIRE_WORK("label_thin_mark");
@@ -443,8 +424,8 @@ extern "C" int emp_label_thin_pass(LT_SWEEP_ARGS, int subfield, int64_t z_base, 
     LT_REQUIRE_HALO("label_thin_pass");
     EMP_REQUIRE(subfield >= 0 && subfield <= 7, "label_thin_pass: subfield = %d outside 0 .. 7", subfield);
     EMP_REQUIRE(z_base >= 0, "label_thin_pass: z_base = %lld is negative", (long long)z_base);
-    EMP_REQUIRE(n_listed >= 0 && n_listed <= lt_tiles(D, H, W).n, "label_thin_pass: %lld listed tiles, the slab has %lld",
-                (long long)n_listed, (long long)lt_tiles(D, H, W).n);
+    EMP_REQUIRE(n_listed >= 0 && n_listed <= emp_tiles(D, H, W).n, "label_thin_pass: %lld listed tiles, the slab has %lld",
+                (long long)n_listed, (long long)emp_tiles(D, H, W).n);
     if (D == 0 || n_listed == 0) return EMP_OK;
     EMP_REQUIRE(lab && state, "label_thin_pass: null pointer");
     LT_REQUIRE_WORK("label_thin_pass");
@@ -601,9 +582,7 @@ __global__ __launch_bounds__(256) void lt_graph_rows_kernel(const T *__restrict_
 
 #define LG2_REQUIRE_SHAPE(what)                                                                                       \
     do {                                                                                                              \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);     \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,        \
-                    (long long)H, (long long)W);                                                                      \
+        EMP_REQUIRE_VOLUME(what);                                                                                     \
         EMP_REQUIRE(H <= LG2_MAX_VOXELS / W && (D == 0 || H * W <= LG2_MAX_VOXELS / D),                               \
                     what ": %lld x %lld x %lld voxels exceed 2^26 per call; cut the slab into z-blocks",              \
                     (long long)D, (long long)H, (long long)W);                                                        \
@@ -614,27 +593,7 @@ __global__ __launch_bounds__(256) void lt_graph_rows_kernel(const T *__restrict_
                     what ": misaligned labels or neighbour slice");                                                   \
     } while (0)
 
-struct LtCountWork {
-    int32_t *counts, *scantmp;
-    int64_t total;
-};
-static LtCountWork lt_count_carve(void *work, int64_t R2)
-{
-    if (R2 < 1) R2 = 1;
-    EmpCarver c(work);
-    LtCountWork L;
-    L.counts = c.take<int32_t>(R2);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R2));
-    L.total = c.bytes();
-    return L;
-}
-extern "C" int64_t emp_label_graph_count_work_bytes(int64_t R) { return R < 0 ? -1 : lt_count_carve(nullptr, 2 * R).total; }
-
-__global__ void lt_zero_kernel(int32_t *__restrict__ v, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        v[i] = 0;
-}
+extern "C" int64_t emp_label_graph_count_work_bytes(int64_t R) { return R < 0 ? -1 : emp_count_carve(nullptr, 2 * R).total; }
 
 template <typename T, bool EMIT>
 static int lt_graph_launch(const void *lab, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
@@ -654,12 +613,12 @@ extern "C" int emp_label_graph_count(const void *lab, int item, int64_t D, int64
     LG2_REQUIRE_SHAPE("label_graph_count");
     EMP_REQUIRE(work && row_offsets, "label_graph_count: null pointer");
     const int64_t R = D * H;
-    LtCountWork L = lt_count_carve(work, 2 * R);
+    EmpCountWork L = emp_count_carve(work, 2 * R);
     EMP_REQUIRE(work_bytes >= L.total, "label_graph_count: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.total);
     hipStream_t st = emp_stream(stream);
     if (R == 0) {
-        EMP_LAUNCH(lt_zero_kernel, 1, 64, st, row_offsets, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
         return EMP_OK;
     }
     const LtGraphOut none = {};
@@ -712,19 +671,6 @@ __global__ void lt_flags_kernel(const uint64_t *__restrict__ keys, const int32_t
     }
 }
 
-// first index in [lo, hi) whose label (the high half) is >= label (UPPER: > label)
-template <bool UPPER>
-__device__ __forceinline__ int64_t lt_label_bound(const uint64_t *__restrict__ keys, int64_t lo, int64_t hi, uint64_t label)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t l = keys[mid] >> 32;
-        if (UPPER ? l <= label : l < label) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // Every sorted key becomes a vertex (z, y, x); the first key of a label opens the label's row of the objects table and
 // closes the row before it.  Different rows, different slots: plain stores.
 __global__ void lt_objects_kernel(const uint64_t *__restrict__ vkeys, int64_t nv, const int32_t *__restrict__ head,
@@ -746,8 +692,8 @@ __global__ void lt_objects_kernel(const uint64_t *__restrict__ vkeys, int64_t nv
                 int64_t *o = objects + row * LG2_OBJ_COLS;
                 o[0] = (int64_t)label;
                 o[1] = i;
-                o[3] = lt_label_bound<false>(ekeys, 0, ne, label);
-                o[4] = lt_label_bound<true>(ekeys, 0, ne, label);
+                o[3] = emp_label_bound<false>(ekeys, 0, ne, label);
+                o[4] = emp_label_bound<true>(ekeys, 0, ne, label);
             }
             if (row > 0 && row - 1 < max_objects) objects[(row - 1) * LG2_OBJ_COLS + 2] = i;
         }
@@ -850,7 +796,7 @@ extern "C" int emp_label_graph_index(const uint64_t *vkeys, const int32_t *vdeg,
     hipStream_t st = emp_stream(stream);
     if (nv == 0) {
         // no vertex: no edge can be resolved
-        EMP_LAUNCH(lt_zero_kernel, 1, 64, st, n_objects, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, n_objects, (int64_t)1);
         if (ne > 0) {
             EMP_REQUIRE(edges, "label_graph_index: null pointer");
             if (hipMemsetAsync(edges, 0xff, (size_t)ne * 2 * sizeof(int32_t), st) != hipSuccess)

@@ -16,28 +16,6 @@
 // bytes of uint32, 4 bytes of uint8) for ANY W and any base offset.  A group cut by the row's ends, and a group of a
 // neighbour row that does not start on such an address (W no multiple of 4, or neighbour slices at another offset), is
 // read voxel by voxel: the narrow path, same values.  A null row and positions outside the row read as 0.
-template <typename T>
-__device__ __forceinline__ void ms_fetch(const T *__restrict__ src, int64_t x, int64_t W, uint32_t (&v)[4])
-{
-    if (src == nullptr) {
-        v[0] = v[1] = v[2] = v[3] = 0u;
-        return;
-    }
-    if (x >= 0 && x + 4 <= W && (reinterpret_cast<uintptr_t>(src + x) & (uintptr_t)(4 * sizeof(T) - 1)) == 0) {
-        if constexpr (sizeof(T) == 4) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(src + x);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-            const uint32_t q = *reinterpret_cast<const uint32_t *>(src + x);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = (q >> (8 * j)) & 0xffu;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (x + j >= 0 && x + j < W) ? (uint32_t)src[x + j] : 0u;
-}
-
 // the run records of a call, indexed by run (row_offsets[row] + position in the row)
 struct MsRuns {
     uint64_t *key;                 // label
@@ -75,13 +53,13 @@ __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab,
         int n_s = 0, n_e = 0;  // wave-uniform running counts of starts / ends in this row
         const int32_t obase = EXTRACT ? row_offsets[row] : 0;
         uint32_t c[4], nx[4];
-        ms_fetch<T>(src, (int64_t)lane * 4 - shift, W, c);
+        emp_fetch4<T>(src, (int64_t)lane * 4 - shift, W, c);
         uint32_t carry = 0u;                                            // voxel left of the chunk (0 at the row start)
         uint32_t sy = 0u, sz = 0u;                                      // exposure sums of the row before this chunk
         for (int64_t x0 = -shift; x0 < W; x0 += 256) {
             const int64_t x = x0 + (int64_t)lane * 4;
             // the next chunk is requested before this one is scanned
-            if (x0 + 256 < W) ms_fetch<T>(src, x + 256, W, nx);
+            if (x0 + 256 < W) emp_fetch4<T>(src, x + 256, W, nx);
             else nx[0] = nx[1] = nx[2] = nx[3] = 0u;
             // a chunk of background alone (wave uniform) starts and ends nothing -- a run that ended on the voxel before
             // it was closed there, against this chunk's first voxel -- and does not wait for the chunk after it
@@ -95,10 +73,10 @@ __global__ __launch_bounds__(256) void ms_rows_kernel(const T *__restrict__ lab,
             // the four loads go out before anything waits for the next chunk
             uint32_t a[4] = {0u, 0u, 0u, 0u}, b[4] = {0u, 0u, 0u, 0u}, f[4] = {0u, 0u, 0u, 0u}, g[4] = {0u, 0u, 0u, 0u};
             if (EXPOSE && (c[0] | c[1] | c[2] | c[3]) != 0u) {
-                ms_fetch<T>(ym, x, W, a);
-                ms_fetch<T>(yp, x, W, b);
-                ms_fetch<T>(zm, x, W, f);
-                ms_fetch<T>(zp, x, W, g);
+                emp_fetch4<T>(ym, x, W, a);
+                emp_fetch4<T>(yp, x, W, b);
+                emp_fetch4<T>(zm, x, W, f);
+                emp_fetch4<T>(zp, x, W, g);
             }
             uint32_t left = __shfl_up(c[3], 1), right = __shfl_down(c[0], 1);
             const uint32_t first_next = __shfl(nx[0], 0);
@@ -199,12 +177,6 @@ __global__ void ms_fix_kernel(MsRuns r, int64_t n)
     }
 }
 
-__global__ void ms_zero_kernel(int32_t *__restrict__ v, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        v[i] = 0;
-}
-
 #define MS_COLS 14
 // sums and maxima start at 0, minima at the largest int64
 __global__ void ms_init_kernel(int64_t *__restrict__ table, int64_t n_rows)
@@ -214,12 +186,6 @@ __global__ void ms_init_kernel(int64_t *__restrict__ table, int64_t n_rows)
         const int col = (int)(i % MS_COLS);
         table[i] = (col >= 2 && col <= 4) ? 0x7fffffffffffffffLL : 0LL;
     }
-}
-
-__global__ void ms_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || keys[i - 1] != keys[i]) ? 1 : 0;
 }
 
 // what one thread has folded of one label; every value is a non-negative integer
@@ -332,10 +298,7 @@ __global__ __launch_bounds__(256) void ms_reduce_kernel(const uint64_t *__restri
 // int32 keeps the scan's int32 total exact whatever the labels are
 #define MS_REQUIRE_SHAPE(what)                                                                                       \
     do {                                                                                                             \
-        EMP_REQUIRE(lab, what ": null pointer");                                                                     \
-        EMP_REQUIRE(item == 1 || item == 4, what ": labels must be uint8 (1) or uint32 (4), got %d bytes", item);    \
-        EMP_REQUIRE(D >= 0 && H > 0 && W > 0, what ": bad shape (D = %lld, H = %lld, W = %lld)", (long long)D,       \
-                    (long long)H, (long long)W);                                                                     \
+        EMP_REQUIRE_LABELS(what);                                                                                    \
         EMP_REQUIRE(H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D),                                  \
                     what ": %lld x %lld x %lld voxels could hold more than 2^31 - 1 runs; cut the slab into z-blocks", \
                     (long long)D, (long long)H, (long long)W);                                                       \
@@ -343,21 +306,7 @@ __global__ __launch_bounds__(256) void ms_reduce_kernel(const uint64_t *__restri
     } while (0)
 
 // ------------------------------------------------------------------------------------------ count + scan
-struct MsCountWork {
-    int32_t *counts, *scantmp;
-    int64_t total;
-};
-static MsCountWork ms_count_carve(void *work, int64_t R)
-{
-    if (R < 1) R = 1;
-    EmpCarver c(work);
-    MsCountWork L;
-    L.counts = c.take<int32_t>(R);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R));
-    L.total = c.bytes();
-    return L;
-}
-extern "C" int64_t emp_label_measure_count_work_bytes(int64_t R) { return ms_count_carve(nullptr, R).total; }
+extern "C" int64_t emp_label_measure_count_work_bytes(int64_t R) { return emp_count_carve(nullptr, R).total; }
 
 template <typename T, bool EXTRACT, bool EXPOSE = EXTRACT>
 static int ms_launch(const void *lab, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
@@ -375,12 +324,12 @@ extern "C" int emp_label_measure_count(const void *lab, int item, int64_t D, int
     MS_REQUIRE_SHAPE("label_measure_count");
     EMP_REQUIRE(work && row_offsets, "label_measure_count: null pointer");
     const int64_t R = D * H;
-    MsCountWork L = ms_count_carve(work, R);
+    EmpCountWork L = emp_count_carve(work, R);
     EMP_REQUIRE(work_bytes >= L.total, "label_measure_count: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.total);
     hipStream_t st = emp_stream(stream);
     if (R == 0) {
-        EMP_LAUNCH(ms_zero_kernel, 1, 64, st, row_offsets, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
         return EMP_OK;
     }
     const MsRuns none = {};
@@ -455,7 +404,7 @@ extern "C" int emp_label_measure(const void *lab, int item, int64_t D, int64_t H
                 (long long)n_runs, (long long)(D * H * W));
     hipStream_t st = emp_stream(stream);
     if (n_runs == 0) {
-        EMP_LAUNCH(ms_zero_kernel, 1, 64, st, n_out, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, n_out, (int64_t)1);
         return EMP_OK;
     }
     EMP_REQUIRE(work && out_table, "label_measure: null pointer");
@@ -473,7 +422,7 @@ extern "C" int emp_label_measure(const void *lab, int item, int64_t D, int64_t H
     return emp_compact(
         L.head, n_runs, L.pos, L.scantmp, n_out, stream, "label_measure: count copy",
         [&]() -> int {
-            EMP_LAUNCH(ms_heads_kernel, grid, 256, st, L.keys_out, n_runs, L.head);
+            EMP_LAUNCH(emp_heads_kernel<0>, grid, 256, st, L.keys_out, n_runs, L.head);
             return EMP_OK;
         },
         [&]() -> int {

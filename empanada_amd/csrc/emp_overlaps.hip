@@ -127,12 +127,6 @@ __global__ void ov_fix_len_kernel(const int32_t *__restrict__ s_start, int32_t *
         s_len[i] -= s_start[i];
 }
 
-template <typename T> __global__ void ov_zero_kernel(T *__restrict__ v, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        v[i] = 0;
-}
-
 static int ov_align0(const void *ptr, int elem) { return (int)((reinterpret_cast<uintptr_t>(ptr) / (uintptr_t)elem) & 3); }
 
 template <typename TG, typename TP, bool EXTRACT>
@@ -184,33 +178,19 @@ static int ov_dispatch(const void *gt, int gt_bytes, const void *pred, int pred_
     } while (0)
 
 // ------------------------------------------------------------------------------------------ count + scan
-struct OvCountWork {
-    int32_t *counts, *scantmp;
-    int64_t total;
-};
-static OvCountWork ov_count_carve(void *work, int64_t R)
-{
-    if (R < 1) R = 1;
-    EmpCarver c(work);
-    OvCountWork L;
-    L.counts = c.take<int32_t>(R);
-    L.scantmp = c.take<int32_t>(emp_scan_tmp_elems(R));
-    L.total = c.bytes();
-    return L;
-}
-extern "C" int64_t emp_label_overlaps_count_work_bytes(int64_t R) { return ov_count_carve(nullptr, R).total; }
+extern "C" int64_t emp_label_overlaps_count_work_bytes(int64_t R) { return emp_count_carve(nullptr, R).total; }
 
 extern "C" int emp_label_overlaps_count(const void *gt, int gt_bytes, const void *pred, int pred_bytes, int64_t R,
                                         int64_t W, void *work, int64_t work_bytes, int32_t *row_offsets, void *stream)
 {
     OV_REQUIRE_SHAPE("label_overlaps_count");
     EMP_REQUIRE(work && row_offsets, "label_overlaps_count: null pointer");
-    OvCountWork L = ov_count_carve(work, R);
+    EmpCountWork L = emp_count_carve(work, R);
     EMP_REQUIRE(work_bytes >= L.total, "label_overlaps_count: workspace too small (%lld < %lld)", (long long)work_bytes,
                 (long long)L.total);
     hipStream_t st = emp_stream(stream);
     if (R == 0) {
-        EMP_LAUNCH(ov_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, row_offsets, (int64_t)1);
         return EMP_OK;
     }
     int rc = ov_dispatch<false>(gt, gt_bytes, pred, pred_bytes, R, W, L.counts, nullptr, nullptr, nullptr, nullptr, st);
@@ -219,12 +199,6 @@ extern "C" int emp_label_overlaps_count(const void *gt, int gt_bytes, const void
 }
 
 // ------------------------------------------------------------------------------------------ extract + sort + reduce
-__global__ void ov_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || keys[i - 1] != keys[i]) ? 1 : 0;
-}
-
 // Every thread sums OV_SEG consecutive sorted spans and adds a partial sum to the pair's count wherever the key changes
 // and at the segment's end: a pair that fills a million spans costs 1/OV_SEG as many atomics, and no thread walks a
 // whole pair alone.  Integer adds, so the order of the atomics does not show in the result.
@@ -291,7 +265,7 @@ extern "C" int emp_label_overlaps(const void *gt, int gt_bytes, const void *pred
                 (long long)n_spans, (long long)(R * W));
     hipStream_t st = emp_stream(stream);
     if (n_spans == 0) {
-        EMP_LAUNCH(ov_zero_kernel<int32_t>, 1, 64, st, n_out, (int64_t)1);
+        EMP_LAUNCH(emp_zero_kernel<int32_t>, 1, 64, st, n_out, (int64_t)1);
         return EMP_OK;
     }
     EMP_REQUIRE(work && out_pairs && out_counts, "label_overlaps: null pointer");
@@ -305,11 +279,11 @@ extern "C" int emp_label_overlaps(const void *gt, int gt_bytes, const void *pred
     EMP_LAUNCH(ov_fix_len_kernel, grid, 256, st, L.start, L.lens_in, n_spans);
     rc = emp_sort_u64_i32(L.keys_in, L.keys_out, L.lens_in, L.lens_out, n_spans, 0, 64, L.cub, L.cub_bytes, stream);
     if (rc != EMP_OK) return rc;
-    EMP_LAUNCH(ov_zero_kernel<int64_t>, grid, 256, st, out_counts, n_spans);
+    EMP_LAUNCH(emp_zero_kernel<int64_t>, grid, 256, st, out_counts, n_spans);
     return emp_compact(
         L.head, n_spans, L.pos, L.scantmp, n_out, stream, "label_overlaps: count copy",
         [&]() -> int {
-            EMP_LAUNCH(ov_heads_kernel, grid, 256, st, L.keys_out, n_spans, L.head);
+            EMP_LAUNCH(emp_heads_kernel<0>, grid, 256, st, L.keys_out, n_spans, L.head);
             return EMP_OK;
         },
         [&]() -> int {

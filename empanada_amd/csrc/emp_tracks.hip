@@ -372,12 +372,6 @@ __global__ void trip_keys_kernel(const int32_t *__restrict__ trip, int64_t n, ui
     }
 }
 
-__global__ void trip_heads_kernel(const uint64_t *__restrict__ keys, int64_t n, int32_t *__restrict__ head)
-{
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || keys[i - 1] != keys[i]) ? 1 : 0;
-}
-
 __global__ void trip_emit_kernel(const uint64_t *__restrict__ keys, const int32_t *__restrict__ vals, int64_t n,
                                  const int32_t *__restrict__ head, const int32_t *__restrict__ pos,
                                  int32_t *__restrict__ out)
@@ -434,7 +428,7 @@ extern "C" int emp_triplets_reduce(const int32_t *trip, int64_t n, void *work, i
     return emp_compact(
         L.head, n, L.pos, L.scantmp, n_out, stream, "triplets_reduce: count copy",
         [&]() -> int {
-            EMP_LAUNCH(trip_heads_kernel, grid, 256, st, L.keys_out, n, L.head);
+            EMP_LAUNCH(emp_heads_kernel<0>, grid, 256, st, L.keys_out, n, L.head);
             return EMP_OK;
         },
         [&]() -> int {

@@ -137,6 +137,43 @@ def pyramid_levels(pyramid, shape3d, world):
     return pyr.check_ranks(shape3d, pyr.normalize(pyramid), sharded.shard_bounds(int(shape3d[0]), world))
 
 
+def _update_attrs(out, attrs):
+    """`attrs` into the attributes of `out` beside what is there already; an `out` without attributes gets none"""
+    if isinstance(out, ZarrV2Group):
+        out.update_attrs(attrs)
+    elif hasattr(out, 'attrs'):
+        out.attrs.update(attrs)
+
+
+def _write_tables(out, group, arrays, rows, attrs):
+    """What the stages that store tables share.  The group's first rank creates one dataset per entry of
+    arrays[key] = {dataset name: numpy array}, one chunk along the rows, writes the arrays that have rows and merges
+    `attrs` into the attributes of `out`.  A store that cannot hold a zero-row array fails the creation: with
+    rows[key] == 0 the key is left out instead, with rows it is an error.  Returns the set of keys left out, the same on
+    every rank: the broadcast also tells the other ranks that the datasets are there to be opened."""
+    rank, world = sharded._world(group)
+    left_out = set()
+    if rank == 0:
+        for key, named in arrays.items():
+            try:
+                for name, a in named.items():
+                    ds = out.create_dataset(name, shape=a.shape, dtype=a.dtype, overwrite=True,
+                                            chunks=(max(a.shape[0], 1),) + tuple(a.shape[1:]))
+                    if a.shape[0]:
+                        ds[...] = a
+            except Exception:
+                if rows[key]:
+                    raise
+                left_out.add(key)
+        _update_attrs(out, attrs)
+    if world > 1:
+        flag = [sorted(left_out, key=str)]
+        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
+        torch.distributed.broadcast_object_list(flag, src=src, group=group)
+        left_out = set(flag[0])
+    return left_out
+
+
 def write_multiscales(out, labels, class_names, levels):
     """one OME-NGFF `multiscales` entry per class into the attributes of `out` (rank 0, after its levels are written):
     entries of other names are kept, one of the same name is replaced; an `out` without attributes gets none"""
@@ -147,10 +184,7 @@ def write_multiscales(out, labels, class_names, levels):
         return
     mine = {e['name'] for e in new}
     kept = [e for e in out.attrs.get('multiscales', []) if not (isinstance(e, dict) and e.get('name') in mine)]
-    if isinstance(out, ZarrV2Group):
-        out.update_attrs({'multiscales': kept + new})
-    else:
-        out.attrs['multiscales'] = kept + new
+    _update_attrs(out, {'multiscales': kept + new})
 
 
 def host_slab(vol, thing):
@@ -276,6 +310,22 @@ def _check_split(split_objects):
     return int(split_objects)
 
 
+def _repairing(finish, thing_list, stats, step):
+    """`finish` with a repair of the thing classes behind it, before anything else reads the volumes: for every thing
+    class, step(c, the class's slab made contiguous, z0, counts) returns the slab to keep and the repair's stats, which
+    `stats` receives as {class: stats}; a step that changes the number of objects writes counts[c]"""
+    def repaired_finish(planes):
+        vols, (z0, z1), counts = finish(planes)
+        counts = dict(counts)
+        for c in vols:
+            if c in thing_list:
+                slab = vols[c] if vols[c].is_contiguous() else vols[c].contiguous()
+                vols[c], stats[c] = step(c, slab, int(z0), counts)
+        return vols, (z0, z1), counts
+
+    return repaired_finish
+
+
 def _splitting(finish, connectivity, thing_list, min_size, min_span, group, stats):
     """`finish` with the repair behind it: every thing class's slab goes through components.split_volume in place, with
     the call's min_size / min_span judged per piece, before anything reads the volumes; the counts become the objects
@@ -284,19 +334,12 @@ def _splitting(finish, connectivity, thing_list, min_size, min_span, group, stat
         return finish
     from ..components import split_volume
 
-    def split_finish(planes):
-        vols, (z0, z1), counts = finish(planes)
-        counts = dict(counts)
-        for c in vols:
-            if c not in thing_list:
-                continue
-            if not vols[c].is_contiguous():
-                vols[c] = vols[c].contiguous()
-            _, stats[c] = split_volume(vols[c], connectivity, min_size, min_span, group=group, z_base=int(z0))
-            counts[c] = stats[c]['objects_out']
-        return vols, (z0, z1), counts
+    def split(c, slab, z0, counts):
+        _, done = split_volume(slab, connectivity, min_size, min_span, group=group, z_base=z0)
+        counts[c] = done['objects_out']
+        return slab, done
 
-    return split_finish
+    return _repairing(finish, thing_list, stats, split)
 
 
 def _check_morph(morph):
@@ -316,21 +359,15 @@ def _morphing(finish, morph, thing_list, shape3d, group, recount, stats):
     from ..morphology import morph_volume
     op, r2, sampling = morph
 
-    def morph_finish(planes):
-        vols, (z0, z1), counts = finish(planes)
-        counts = dict(counts)
-        for c in vols:
-            if c not in thing_list:
-                continue
-            slab = vols[c] if vols[c].is_contiguous() else vols[c].contiguous()
-            vols[c], stats[c] = morph_volume(slab, shape3d, op, r2, sampling, group=group, z_base=int(z0))
-            if recount and op in ('erode', 'open'):
-                below, above = _neighbour_slices(vols[c], group)
-                table = gather_tables(_hip.measure_labels(vols[c], below=below, above=above, z_base=int(z0)), group)
-                counts[c] = int(table.shape[0])
-        return vols, (z0, z1), counts
+    def morphed(c, slab, z0, counts):
+        vol, done = morph_volume(slab, shape3d, op, r2, sampling, group=group, z_base=z0)
+        if recount and op in ('erode', 'open'):
+            below, above = _neighbour_slices(vol, group)
+            table = gather_tables(_hip.measure_labels(vol, below=below, above=above, z_base=z0), group)
+            counts[c] = int(table.shape[0])
+        return vol, done
 
-    return morph_finish
+    return _repairing(finish, thing_list, stats, morphed)
 
 
 def _check_separate(separate):
@@ -349,20 +386,13 @@ def _separating(finish, separate, thing_list, shape3d, group, recount, stats):
     from ..separation import separate_volume
     r2, min_core, sampling = separate
 
-    def separate_finish(planes):
-        vols, (z0, z1), counts = finish(planes)
-        counts = dict(counts)
-        for c in vols:
-            if c not in thing_list:
-                continue
-            if not vols[c].is_contiguous():
-                vols[c] = vols[c].contiguous()
-            _, stats[c] = separate_volume(vols[c], shape3d, r2, min_core, sampling, group=group, z_base=int(z0))
-            if recount:
-                counts[c] = int(counts[c]) + stats[c]['pieces_added']
-        return vols, (z0, z1), counts
+    def separated(c, slab, z0, counts):
+        _, done = separate_volume(slab, shape3d, r2, min_core, sampling, group=group, z_base=z0)
+        if recount:
+            counts[c] = int(counts[c]) + done['pieces_added']
+        return slab, done
 
-    return separate_finish
+    return _repairing(finish, thing_list, stats, separated)
 
 
 def _check_fill(fill_holes):
@@ -384,17 +414,11 @@ def _filling(finish, wanted, max_voxels, thing_list, shape3d, group, stats):
         return finish
     from ..holes import fill_volume
 
-    def fill_finish(planes):
-        vols, (z0, z1), counts = finish(planes)
-        for c in vols:
-            if c not in thing_list:
-                continue
-            if not vols[c].is_contiguous():
-                vols[c] = vols[c].contiguous()
-            _, stats[c] = fill_volume(vols[c], shape3d, max_voxels, group=group, z_base=int(z0))
-        return vols, (z0, z1), counts
+    def filled(c, slab, z0, counts):
+        _, done = fill_volume(slab, shape3d, max_voxels, group=group, z_base=z0)
+        return slab, done
 
-    return fill_finish
+    return _repairing(finish, thing_list, stats, filled)
 
 
 def _measured(res, spacing, labels, class_names, out, group):
@@ -404,7 +428,6 @@ def _measured(res, spacing, labels, class_names, out, group):
     if spacing is None:
         return res
     from ..measurements import COLUMNS, gather_tables
-    rank, world = sharded._world(group)
     z0 = int(res['z_range'][0])
     objects = {}
     for c in labels:
@@ -416,30 +439,11 @@ def _measured(res, spacing, labels, class_names, out, group):
     if out is None:
         return res
     names = object_dataset_names(labels, class_names)
-    left_out = set()
-    if rank == 0:
-        for c in labels:
-            table = objects[c]
-            try:
-                ds = out.create_dataset(names[c], shape=table.shape, dtype=np.int64, overwrite=True,
-                                        chunks=(max(table.shape[0], 1), table.shape[1]))
-                if table.shape[0]:
-                    ds[...] = table
-            except Exception:
-                if table.shape[0]:
-                    raise
-                left_out.add(c)                      # a store that cannot hold a zero-row array
-        attrs = {'objects': {'columns': list(COLUMNS), 'spacing': list(spacing)}}
-        if isinstance(out, ZarrV2Group):
-            out.update_attrs(attrs)
-        elif hasattr(out, 'attrs'):
-            out.attrs.update(attrs)
-    if world > 1:
-        flag = [sorted(left_out, key=str)]
-        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
-        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
-        left_out = set(flag[0])
-    res['object_datasets'] = {c: None if c in left_out else out[names[c]] for c in labels}
+    assert all(t.dtype == np.int64 for t in objects.values())
+    missing = _write_tables(out, group, {c: {names[c]: objects[c]} for c in labels},
+                            {c: objects[c].shape[0] for c in labels},
+                            {'objects': {'columns': list(COLUMNS), 'spacing': list(spacing)}})
+    res['object_datasets'] = {c: None if c in missing else out[names[c]] for c in labels}
     return res
 
 
@@ -460,7 +464,6 @@ def _meshed(res, iterations, thing_list, shape3d, class_names, out, group):
     if iterations is None:
         return res
     from ..meshes import OBJECT_COLUMNS, mesh_volume
-    rank, world = sharded._world(group)
     z0 = int(res['z_range'][0])
     classes = [c for c in res['volumes'] if c in thing_list]
     meshes = {}
@@ -471,30 +474,11 @@ def _meshed(res, iterations, thing_list, shape3d, class_names, out, group):
     if out is None:
         return res
     names = mesh_dataset_names(classes, class_names)
-    left_out = set()
-    if rank == 0:
-        for c in classes:
-            try:
-                for k, a in meshes[c].items():
-                    ds = out.create_dataset(names[c][k], shape=a.shape, dtype=a.dtype, overwrite=True,
-                                            chunks=(max(a.shape[0], 1), a.shape[1]))
-                    if a.shape[0]:
-                        ds[...] = a
-            except Exception:
-                if meshes[c]['objects'].shape[0]:
-                    raise
-                left_out.add(c)                      # a store that cannot hold a zero-row array
-        attrs = {'meshes': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS), 'iterations': int(iterations)}}
-        if isinstance(out, ZarrV2Group):
-            out.update_attrs(attrs)
-        elif hasattr(out, 'attrs'):
-            out.attrs.update(attrs)
-    if world > 1:
-        flag = [sorted(left_out, key=str)]
-        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
-        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
-        left_out = set(flag[0])
-    res['mesh_datasets'] = {c: None if c in left_out else {k: out[names[c][k]] for k in names[c]} for c in classes}
+    missing = _write_tables(out, group, {c: {names[c][k]: a for k, a in meshes[c].items()} for c in classes},
+                            {c: meshes[c]['objects'].shape[0] for c in classes},
+                            {'meshes': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS),
+                                        'iterations': int(iterations)}})
+    res['mesh_datasets'] = {c: None if c in missing else {k: out[names[c][k]] for k in names[c]} for c in classes}
     return res
 
 
@@ -518,7 +502,6 @@ def _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group):
         return res
     from ..skeletons import OBJECT_COLUMNS, skeleton_volume
     r_cap, cap, sampling = skeleton
-    rank, world = sharded._world(group)
     z0 = int(res['z_range'][0])
     classes = [c for c in res['volumes'] if c in thing_list]
     skeletons = {}
@@ -529,31 +512,11 @@ def _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group):
     if out is None:
         return res
     names = skeleton_dataset_names(classes, class_names)
-    left_out = set()
-    if rank == 0:
-        for c in classes:
-            try:
-                for k, a in skeletons[c].items():
-                    ds = out.create_dataset(names[c][k], shape=a.shape, dtype=a.dtype, overwrite=True,
-                                            chunks=(max(a.shape[0], 1),) + tuple(a.shape[1:]))
-                    if a.shape[0]:
-                        ds[...] = a
-            except Exception:
-                if skeletons[c]['objects'].shape[0]:
-                    raise
-                left_out.add(c)                      # a store that cannot hold a zero-row array
-        attrs = {'skeletons': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS), 'r_cap': float(r_cap),
-                               'sampling': [int(a) for a in sampling]}}
-        if isinstance(out, ZarrV2Group):
-            out.update_attrs(attrs)
-        elif hasattr(out, 'attrs'):
-            out.attrs.update(attrs)
-    if world > 1:
-        flag = [sorted(left_out, key=str)]
-        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
-        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
-        left_out = set(flag[0])
-    res['skeleton_datasets'] = {c: None if c in left_out else {k: out[names[c][k]] for k in names[c]} for c in classes}
+    missing = _write_tables(out, group, {c: {names[c][k]: a for k, a in skeletons[c].items()} for c in classes},
+                            {c: skeletons[c]['objects'].shape[0] for c in classes},
+                            {'skeletons': {'axes': 'zyx', 'object_columns': list(OBJECT_COLUMNS), 'r_cap': float(r_cap),
+                                           'sampling': [int(a) for a in sampling]}})
+    res['skeleton_datasets'] = {c: None if c in missing else {k: out[names[c][k]] for k in names[c]} for c in classes}
     return res
 
 
@@ -587,7 +550,6 @@ def _contacted(res, contacts, class_names, out, group):
         return res
     from ..contacts import COLUMNS, gather_tables, halo_slices
     r2, sampling, pairs = contacts
-    rank, world = sharded._world(group)
     z0 = int(res['z_range'][0])
     halo = halo_slices(r2, sampling)
     slabs = {c: res['volumes'][c].contiguous() for c in {c for p in pairs for c in p}}
@@ -602,31 +564,12 @@ def _contacted(res, contacts, class_names, out, group):
     if out is None:
         return res
     names = contact_dataset_names(pairs, class_names)
-    left_out = set()
-    if rank == 0:
-        for p in pairs:
-            table = tables[p]
-            try:
-                ds = out.create_dataset(names[p], shape=table.shape, dtype=np.int64, overwrite=True,
-                                        chunks=(max(table.shape[0], 1), table.shape[1]))
-                if table.shape[0]:
-                    ds[...] = table
-            except Exception:
-                if table.shape[0]:
-                    raise
-                left_out.add(p)                      # a store that cannot hold a zero-row array
-        attrs = {'contacts': {'columns': list(COLUMNS), 'r2': int(r2), 'sampling': [int(a) for a in sampling],
-                              'pairs': [[ca, cb] for ca, cb in pairs]}}
-        if isinstance(out, ZarrV2Group):
-            out.update_attrs(attrs)
-        elif hasattr(out, 'attrs'):
-            out.attrs.update(attrs)
-    if world > 1:
-        flag = [sorted(left_out, key=str)]
-        src = 0 if group is None else torch.distributed.get_global_rank(group, 0)
-        torch.distributed.broadcast_object_list(flag, src=src, group=group)   # also: rank 0 has written before any opens
-        left_out = set(flag[0])
-    res['contact_datasets'] = {p: None if p in left_out else out[names[p]] for p in pairs}
+    assert all(t.dtype == np.int64 for t in tables.values())
+    missing = _write_tables(out, group, {p: {names[p]: tables[p]} for p in pairs},
+                            {p: tables[p].shape[0] for p in pairs},
+                            {'contacts': {'columns': list(COLUMNS), 'r2': int(r2), 'sampling': [int(a) for a in sampling],
+                                          'pairs': [[ca, cb] for ca, cb in pairs]}})
+    res['contact_datasets'] = {p: None if p in missing else out[names[p]] for p in pairs}
     return res
 
 

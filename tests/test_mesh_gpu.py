@@ -104,6 +104,37 @@ def test_neighbour_slices_stand_for_the_volume_around(dtype):
     _assert_mesh(got, mesh_ref(big))
 
 
+@pytest.mark.parametrize('offset', [1, 2, 3])
+def test_unaligned_slab_takes_the_narrow_path(offset):
+    """the slab starts 1, 2 or 3 elements off a 16-byte (uint32) / 4-byte (uint8) address and its neighbour slices at yet
+    another offset; W = 7 cuts a group at both ends of every row, and the rows of 7 elements put the aligned load and the
+    voxel-by-voxel one on different rows: same keys, same quads, same mesh"""
+    from empanada_amd import _hip
+    shape = (3, 5, 7)
+    for dtype, tdt in ((np.uint32, torch.int32), (np.uint8, torch.uint8)):
+        a = random_volume(shape, seed=40 + offset, density=0.5, dtype=dtype, big=dtype == np.uint32)
+        ends = random_volume((2,) + shape[1:], seed=50 + offset, density=0.5, dtype=dtype)
+        flat = torch.zeros((a.size + ends.size + 32,), dtype=tdt, device='cuda')
+        flat[offset:offset + a.size] = _dev(a).view(tdt).ravel()
+        at = offset + a.size
+        at += (offset + 2 - at) % 4                                         # the neighbour slices at yet another offset
+        flat[at:at + ends.size] = _dev(ends).view(tdt).ravel()
+        view = (lambda t: t.view(torch.uint32)) if dtype == np.uint32 else (lambda t: t)
+        dev = view(flat[offset:offset + a.size]).view(a.shape)
+        nb = view(flat[at:at + ends.size]).view(ends.shape)
+        assert dev.data_ptr() % (4 * dev.element_size()) != 0 and dev.is_contiguous()
+        assert nb.data_ptr() % (4 * nb.element_size()) != dev.data_ptr() % (4 * dev.element_size())
+        keys, (qk, qd) = _hip.label_mesh(dev, below=nb[0], above=nb[1], z_base=2)
+        wk, wq, wd = emit_ref(a, below=ends[0], above=ends[1], z_base=2)
+        np.testing.assert_array_equal(np.sort(_u64(keys)), wk, err_msg=str(dtype))
+        np.testing.assert_array_equal(_u64(qk), wq, err_msg=str(dtype))
+        np.testing.assert_array_equal(qd.cpu().numpy(), wd, err_msg=str(dtype))
+        got = dict(zip(('vertices', 'quads', 'objects'),
+                       (t.cpu().numpy() for t in _hip.mesh_finish(keys, (qk, qd), shape))))
+        _assert_mesh(got, finish_ref(wk, wq, wd, shape[1], shape[2]))
+        assert len(wq) and (a != 0).any() and (ends != 0).any()
+
+
 @pytest.mark.parametrize('slices', [1, 2])
 def test_z_blocks_equal_the_uncut_call(slices):
     from empanada_amd import _hip
