@@ -161,6 +161,10 @@ SIGNATURES = {
     'emp_label_contacts_rows_work_bytes': (_L, [_L]),
     'emp_label_contacts_rows': (_I, [_P, _L, _P, _L, _P, _P]),
     'emp_label_contacts_reduce': (_I, [_P, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
+    'emp_label_thick_work_bytes': (_L, [_L, _L, _L, _L, _L]),
+    'emp_label_thick_edt': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
+    'emp_label_thick_lists': (_I, [_L, _L, _L, _L, _L, _I, _P, _L, _P, _P]),
+    'emp_label_thick_resolve': (_I, [_L, _L, _L, _L, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
     'emp_mesh_neighbours': (_I, [_P, _L, _P, _L, _P, _P]),
     'emp_mesh_smooth': (_I, [_P, _P, _L, _F, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
@@ -2250,6 +2254,130 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
         return tables[0]
     from .contacts import merge_tables
     return merge_tables(tables)
+
+
+THICK_MAX_VOXELS = MEASURE_MAX_VOXELS         # voxels per emp_label_thick_* call, halos included
+THICK_BLOCK_VOXELS = 2 ** 28                 # a z-block's own voxels by default: 8 bytes of workspace per voxel
+THICK_COLUMNS = 3
+
+
+def _z_stack(slab, lo, hi, below, above):
+    """The slices [lo, hi) of a slab continued by the caller's stacks beyond its ends -- lo may be negative and hi
+    exceed D -- as far as there are any: (tensor or None, slices).  A view where one part suffices."""
+    D = int(slab.shape[0])
+    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
+    parts = []
+    if lo < 0 and n_below:
+        parts.append(below[max(n_below + lo, 0):])
+    if max(lo, 0) < min(hi, D):
+        parts.append(slab[max(lo, 0):min(hi, D)])
+    if hi > D and n_above:
+        parts.append(above[:min(hi - D, n_above)])
+    parts = [p for p in parts if p.shape[0]]
+    if not parts:
+        return None, 0
+    if len(parts) == 1:
+        return parts[0], int(parts[0].shape[0])
+    u32 = slab.dtype == torch.uint32                                   # torch copies few uint32 tensors
+    both = torch.cat([p.view(torch.int32) if u32 else p for p in parts])
+    return (both.view(torch.uint32) if u32 else both), int(both.shape[0])
+
+
+def label_thickness(slab, cap=1024, sampling=(1, 1, 1), below=None, above=None, block_voxels=None, info=None):
+    """The local thickness of the labelled objects (emp_label_thick_*; the definition is in include/emp_hip.h, E10):
+    (t2, table).  t2 is a (D, H, W) uint16 tensor on the slab's device, T2(p) = the largest label_edt value d2(q), capped
+    at `cap` (1 .. 65535), among the voxels q with |p - q|^2 < d2(q): the squared radius of the largest ball that fits
+    its object and covers p, 0 on background; the diameter is 2 sqrt(T2) in units of the sampling.  The cap is part of
+    the definition, not a clamp of the uncapped result.  table is (m, 3) int64 on the device, rows (label, t2, voxels)
+    ascending by (label, t2) with the label as an unsigned 32-bit value (thickness.COLUMNS): the exact histogram of t2
+    per object.  slab: (D, H, W), contiguous, on the GPU, uint8 or int32 / uint32 (the bits are taken as they are); it is
+    never written.  sampling: the voxel pitch (az, ay, ax), integers in 1 .. 16.  below / above: (h, H, W) stacks of the
+    slab's dtype and device that stand for the slices z = -h .. -1 and z = D .. D + h - 1, None = the volume's face; with
+    2 * (isqrt(cap - 1) // az) slices the result is that of the undivided volume, with fewer that of the volume cut
+    there.  A slab of more than block_voxels voxels (None: THICK_BLOCK_VOXELS) is cut into z-blocks of whole slices, each
+    with that many halo slices per side -- views of the slab, continued by below / above at its ends; a block with its
+    halos may hold THICK_MAX_VOXELS voxels, and a single slice above the limit is refused.  The tables of the blocks are
+    merged on the device (thickness.merge_tables).  Every argument error, a CPU tensor among them, is a ValueError
+    before any GPU work; an empty slab gives an empty map and a (0, 3) table.  info: a dict that receives 'blocks',
+    'work_bytes' (largest workspace of one call), 'candidates' (voxels listed as ball centres, halos included),
+    'capped' (voxels of the slab with d2 == cap: 0 means the result is the uncapped one), 'lists' (tiles with a list)
+    and 'longest' (the longest list)."""
+    import math
+    name = 'label_thickness'
+    cap = _label_int(name, "cap", cap, 1, 65535)
+    az, ay, ax = sampling = _morph_sampling(name, sampling)
+    block_voxels = _block_voxels(name, block_voxels, THICK_MAX_VOXELS) if block_voxels is not None else None
+    slab = _label_operand(name, "slab", slab)
+    if slab.dim() != 3:
+        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    D, H, W = (int(s) for s in slab.shape)
+    dev = slab.device
+    if below is not None:
+        below = _label_operand(name, "below", below, slab.dtype, (None, H, W), dev)
+    if above is not None:
+        above = _label_operand(name, "above", above, slab.dtype, (None, H, W), dev)
+    stats = {} if info is None else info
+    stats.update(blocks=0, work_bytes=0, candidates=0, capped=0, lists=0, longest=0)
+    t2 = torch.empty((D, H, W), dtype=torch.uint16, device=dev)
+    empty = torch.zeros((0, THICK_COLUMNS), dtype=torch.int64, device=dev)
+    if slab.numel() == 0:
+        return t2, empty
+    halo = 2 * (math.isqrt(cap - 1) // az)
+    if block_voxels is None:
+        _block_slices(name, H, W, THICK_MAX_VOXELS)
+        per = max(1, min(THICK_BLOCK_VOXELS // (H * W), THICK_MAX_VOXELS // (H * W) - 2 * halo))
+    else:
+        per = _block_slices(name, H, W, block_voxels)
+    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
+    for z0 in range(0, D, per):
+        z1 = min(D, z0 + per)
+        total = min(halo, z0 + n_below) + z1 - z0 + min(halo, D - z1 + n_above)
+        if total * H * W > THICK_MAX_VOXELS:
+            raise ValueError(f"{name}: a block of {z1 - z0} slices of {H} x {W} with its halo slices is {total * H * W} "
+                             f"voxels, above the limit of {THICK_MAX_VOXELS} voxels per call")
+    require_gpu()
+    item = slab.element_size()
+    tables = []
+    with torch.cuda.device(dev):
+        for z0 in range(0, D, per):
+            z1 = min(D, z0 + per)
+            d = z1 - z0
+            lo, hb = _z_stack(slab, z0 - halo, z0, below, above)
+            hi, ha = _z_stack(slab, z1, z1 + halo, below, above)
+            wb = query('emp_label_thick_work_bytes', d, H, W, hb, ha)
+            if wb < 0:
+                raise ValueError(f"{name}: ({hb} + {d} + {ha}) x {H} x {W} voxels exceed the limit of "
+                                 f"{THICK_MAX_VOXELS} voxels per call, halos included")
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            totals = torch.empty((4,), dtype=torch.int64, device=dev)
+            n_ext = (hb + d + ha) * H * W
+            call('emp_label_thick_edt', _ptr(slab[z0:z1]), item, d, H, W, _ptr(lo), hb, _ptr(hi), ha, az, ay, ax, cap,
+                 _ptr(work), wb, _current_stream(), alg_bytes=n_ext * (item + 2))
+            call('emp_label_thick_lists', d, H, W, hb, ha, cap, _ptr(work), wb, _ptr(totals), _current_stream(),
+                 alg_bytes=n_ext * 6)
+            call('emp_label_thick_resolve', d, H, W, hb, ha, az, ay, ax, cap, _ptr(work), wb, _ptr(t2[z0:z1]),
+                 _current_stream(), alg_bytes=n_ext * 6 + d * H * W * 2)
+            del work, lo, hi
+            # the per-object histogram: the pair table of (label, t2) -- emp_label_overlaps reads 1- and 4-byte items,
+            # so it gets a widened copy of the block's t2
+            wide = t2[z0:z1].view(torch.int16).to(torch.int32) & 0xffff
+            pairs, counts = label_overlaps(slab[z0:z1], wide)
+            del wide
+            if pairs.shape[0]:
+                tables.append(torch.cat([pairs, counts[:, None]], dim=1))
+            cand, capped, lists, longest = (int(v) for v in totals.tolist())
+            stats['blocks'] += 1
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            stats['candidates'] += cand
+            stats['capped'] += capped
+            stats['lists'] += lists
+            stats['longest'] = max(stats['longest'], longest)
+    if not tables:
+        return t2, empty
+    if len(tables) == 1:
+        return t2, tables[0]
+    from .thickness import merge_tables
+    return t2, merge_tables(tables)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

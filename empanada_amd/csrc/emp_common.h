@@ -216,6 +216,13 @@ static inline bool emp_tiles_shape_ok(int64_t D, int64_t H, int64_t W)
     return D >= 0 && H > 0 && W > 0 && H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D);
 }
 
+// emp_label_morph.hip: emp_label_edt's three passes with EVERY slice of the extended volume (hb + D + ha slices) as
+// output: d2[ze] is the distance inside that volume, whose first and last slices are faces.  d2 and tmp hold one uint16
+// per voxel of the extended volume each; the shape must have passed the checks of emp_label_edt_work_bytes.
+int emp_label_edt_extended(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                           const void *above, int64_t ha, int az, int ay, int ax, int cap, uint16_t *d2, uint16_t *tmp,
+                           void *stream);
+
 // emp_measure.hip: the run extraction of its rows kernel without the neighbour rows (see there)
 int emp_label_rows_extract(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
                            int64_t n_runs, int32_t *row, int32_t *xs, int32_t *xe, uint32_t *val, void *stream);

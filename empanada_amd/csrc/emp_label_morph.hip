@@ -166,7 +166,8 @@ __global__ __launch_bounds__(256) void mo_edt_y_kernel(MoVol<T> vol, uint32_t n,
 
 // the z pass over the core slices: g is indexed by the extended volume, the output by the core.  ERODE: the label
 // where the distance exceeds r2 = cap - 1, 0 elsewhere, in the labels' own type; otherwise the distance as uint16.
-template <typename T, bool ERODE>
+// ALL: the output is indexed by the extended volume too (emp_label_edt_extended), every slice of it a core slice.
+template <typename T, bool ERODE, bool ALL = false>
 __global__ __launch_bounds__(256) void mo_edt_z_kernel(MoVol<T> vol, uint32_t n, uint32_t HW, int w, int cap,
                                                        const uint16_t *__restrict__ g, void *__restrict__ out)
 {
@@ -174,8 +175,8 @@ __global__ __launch_bounds__(256) void mo_edt_z_kernel(MoVol<T> vol, uint32_t n,
     const int64_t Z = vol.hb + vol.D + vol.ha;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const uint32_t z = i / HW, p = i - z * HW;
-        const int64_t ze = (int64_t)z + vol.hb;
-        const uint32_t l = (uint32_t)vol.lab[i];
+        const int64_t ze = ALL ? (int64_t)z : (int64_t)z + vol.hb;
+        const uint32_t l = ALL ? (uint32_t)vol.slice(ze)[p] : (uint32_t)vol.lab[i];
         int best = 0;
         if (l != 0u) {
             best = g[ze * HW + p];
@@ -380,7 +381,7 @@ extern "C" int64_t emp_label_dilate_work_bytes(int64_t D, int64_t H, int64_t W, 
     return mo_work_bytes(D, H, W, hb, ha, true);
 }
 
-template <typename T, bool ERODE>
+template <typename T, bool ERODE, bool ALL = false>
 static int mo_edt_launch(const MoShape &S, const void *lab, const void *below, const void *above, int az, int ay, int ax,
                          int cap, const MoEdtWork &L, void *out, hipStream_t st)
 {
@@ -390,7 +391,8 @@ static int mo_edt_launch(const MoShape &S, const void *lab, const void *below, c
     EMP_LAUNCH((mo_edt_rows_kernel<T>), emp_grid(rows * 64, 256, 16384), 256, st, vol, rows, S.H, S.W, ax * ax, cap, L.f);
     EMP_LAUNCH((mo_edt_y_kernel<T>), emp_grid(S.n_ext, 256, 16384), 256, st, vol, (uint32_t)S.n_ext, (uint32_t)S.H,
                (uint32_t)S.W, ay * ay, L.f, L.g);
-    EMP_LAUNCH((mo_edt_z_kernel<T, ERODE>), emp_grid(S.n_core, 256, 16384), 256, st, vol, (uint32_t)S.n_core,
+    const int64_t n_out = ALL ? S.n_ext : S.n_core;
+    EMP_LAUNCH((mo_edt_z_kernel<T, ERODE, ALL>), emp_grid(n_out, 256, 16384), 256, st, vol, (uint32_t)n_out,
                (uint32_t)(S.H * S.W), az * az, cap, L.g, out);
     return EMP_OK;
 }
@@ -420,6 +422,25 @@ extern "C" int emp_label_edt(const void *lab, int item, int64_t D, int64_t H, in
     EMP_REQUIRE(cap >= 1 && cap <= 65535, "label_edt: cap = %d outside 1 .. 65535", cap);
     return mo_edt_run("label_edt", lab, item, mo_shape(D, H, W, hb, ha), below, above, az, ay, ax, cap, work, work_bytes,
                       out, false, stream);
+}
+
+// the x pass writes `d2`, the y pass reads it and writes `tmp`, the z pass reads `tmp` and writes `d2`
+int emp_label_edt_extended(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                           const void *above, int64_t ha, int az, int ay, int ax, int cap, uint16_t *d2, uint16_t *tmp,
+                           void *stream)
+{
+    MO_REQUIRE_ARGS("label_edt_extended");
+    EMP_REQUIRE(cap >= 1 && cap <= 65535, "label_edt_extended: cap = %d outside 1 .. 65535", cap);
+    const MoShape S = mo_shape(D, H, W, hb, ha);
+    if (S.n_ext == 0) return EMP_OK;
+    EMP_REQUIRE(d2 && tmp, "label_edt_extended: null pointer");
+    MoEdtWork L;
+    L.f = d2;
+    L.g = tmp;
+    L.total = 0;
+    hipStream_t st = emp_stream(stream);
+    return item == 4 ? mo_edt_launch<uint32_t, false, true>(S, lab, below, above, az, ay, ax, cap, L, d2, st)
+                     : mo_edt_launch<uint8_t, false, true>(S, lab, below, above, az, ay, ax, cap, L, d2, st);
 }
 
 extern "C" int emp_label_erode(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,

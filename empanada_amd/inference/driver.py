@@ -573,6 +573,59 @@ def _contacted(res, contacts, class_names, out, group):
     return res
 
 
+def _check_thickness(thickness):
+    """infer_volume's `thickness` argument -> None or (r_cap, cap, sampling), before any GPU work"""
+    from ..thickness import check
+    return check(thickness)
+
+
+def thickness_dataset_names(classes, class_names):
+    return {c: f"{(class_names or {}).get(c, c)}_thickness" for c in classes}
+
+
+def _thickened(res, thickness, thing_list, shape3d, class_names, out, group):
+    """The result with 'thickness' and 'thickness_maps': every rank computes the map of its slab of every thing class
+    with halo slices from the ranks next to it (thickness.thickness_volume) and the tables are merged over the ranks.
+    With `out`, rank 0 creates one '<class name>_thickness' dataset per class -- uint16, the labels' shape, chunks
+    (1, Y, X), always raw chunks: write_slab_device takes 1- and 4-byte items only, and a 2-byte device deflate is not
+    built -- every rank writes its slab of it, and rank 0 writes the '<class name>_thickness_table' datasets"""
+    if thickness is None:
+        return res
+    from ..thickness import COLUMNS, thickness_volume
+    r_cap, cap, sampling = thickness
+    rank, world = sharded._world(group)
+    z0 = int(res['z_range'][0])
+    classes = [c for c in res['volumes'] if c in thing_list]
+    tables, maps = {}, {}
+    for c in classes:
+        stats = {}
+        maps[c], table = thickness_volume(res['volumes'][c], group, cap, sampling, info=stats)
+        tables[c] = {'table': table.cpu().numpy(), 'capped': int(stats['capped'])}
+    res['thickness'] = tables
+    res['thickness_maps'] = maps
+    res['thickness_params'] = {'r_cap': float(r_cap), 'cap': int(cap), 'sampling': tuple(int(a) for a in sampling)}
+    if out is None:
+        return res
+    names = thickness_dataset_names(classes, class_names)
+    if rank == 0:
+        for c in classes:
+            out.create_dataset(names[c], shape=tuple(int(s) for s in shape3d), dtype=np.uint16, overwrite=True,
+                               chunks=(1, None, None))
+    if world > 1:
+        torch.distributed.barrier(group=group)
+    for c in classes:
+        if maps[c].shape[0]:
+            out[names[c]].write_slab(z0, maps[c].view(torch.int16).cpu().numpy().view(np.uint16))
+    missing = _write_tables(out, group, {c: {names[c] + '_table': tables[c]['table']} for c in classes},
+                            {c: tables[c]['table'].shape[0] for c in classes},
+                            {'thickness': {'columns': list(COLUMNS), 'r_cap': float(r_cap), 'cap': int(cap),
+                                           'sampling': [int(a) for a in sampling],
+                                           'map': 'squared radius, diameter = 2 sqrt'}})
+    res['thickness_datasets'] = {c: {'map': out[names[c]], 'table': None if c in missing else out[names[c] + '_table']}
+                                 for c in classes}
+    return res
+
+
 @torch.no_grad()
 def _plane_windowed(engine, dv, axis, n, batch_pixels, render_steps, params, window_slices, mem_budget, info):
     """one plane through windowed.windowed_panoptic_stack: the model forward of _plane_heads is the `fill`"""
@@ -601,7 +654,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
                  measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None,
-                 skeleton=None, contacts=None):
+                 skeleton=None, contacts=None, thickness=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -736,6 +789,23 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     one dataset '<class a name>_<class b name>_contacts' per pair (int64, (n, 10), one raw chunk), the group's
     attributes gain 'contacts': {'columns', 'r2', 'sampling', 'pairs'}, and the result gains 'contact_datasets': {(ca,
     cb): array, or None where the store cannot hold a zero-row table}.
+    thickness: None = no map, no new key, no launch; True (r_cap = 32), r_cap or (r_cap, (az, ay, ax)) (thickness.check;
+    r_cap is the largest radius reported, >= 1 in the units of the integer sampling, cap = floor(r_cap^2) <= 65535) = once
+    the volumes are final, where measure, mesh, skeleton and contacts run, every thing class gets its local thickness,
+    computed on the device (_hip.label_thickness; include/emp_hip.h, E10): T2(p) is the squared radius, capped at cap,
+    of the largest ball that fits the object and covers p -- not the one centred on p -- so the diameter at p is 2
+    sqrt(T2(p)), with the voxel-centre bias of the edt (a line one voxel wide reads 2).  Every rank fetches 2
+    (isqrt(cap - 1) // az) slices per side from the ranks next to it, so the map is that of the undivided volume.  The
+    result gains 'thickness': {class: {'table': (m, 3) int64 numpy of the WHOLE volume, the same on every rank, rows
+    (label, t2, voxels) ascending -- thickness.COLUMNS; thickness.derive and thickness.histogram read it --, 'capped':
+    voxels of the whole volume whose distance reached the cap; 0 means the map is the uncapped one}},
+    'thickness_maps': {class: the rank's (z1 - z0, Y, X) uint16 device slab of T2} and 'thickness_params': {'r_cap',
+    'cap', 'sampling'}.  With out=, rank 0 creates one dataset '<class name>_thickness' per class (uint16, the labels'
+    shape, chunks (1, Y, X)) and every rank writes its slab of it -- always raw chunks, whatever `compressor` says:
+    write_slab_device takes 1- and 4-byte items only and a 2-byte device deflate is not built --, rank 0 writes the table
+    as '<class name>_thickness_table' (int64, (m, 3), one raw chunk), the group's attributes gain 'thickness':
+    {'columns', 'r_cap', 'cap', 'sampling', 'map': 'squared radius, diameter = 2 sqrt'}, and the result gains
+    'thickness_datasets': {class: {'map': array, 'table': array, or None where the store cannot hold a zero-row table}}.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -748,6 +818,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     separate = _check_separate(separate)
     mesh_iterations = _check_mesh(mesh)
     skeleton = _check_skeleton(skeleton)
+    thickness = _check_thickness(thickness)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -819,7 +890,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         res = _measured(_scored(res, ground_truth, thing_list, group), spacing, labels, class_names, out, group)
         res = _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
         res = _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group)
-        return _contacted(res, contacts, class_names, out, group)
+        res = _contacted(res, contacts, class_names, out, group)
+        return _thickened(res, thickness, thing_list, shape3d, class_names, out, group)
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,

@@ -1133,6 +1133,51 @@ int emp_label_contacts_reduce(const uint64_t *keys, const int32_t *perm, const i
                               int64_t n, int64_t H, int64_t W, int64_t z_base, const void *work, int64_t work_bytes,
                               int64_t *table, int64_t n_rows, void *stream);
 
+/* ---- E10: local thickness of the labelled objects -- the largest inscribed ball that covers a voxel ---------------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact: ImageJ / BoneJ "Local Thickness" or
+ *          a loop over the objects with an edt each (Hildebrand and Ruegsegger's definition).
+ * Setting.  L is a label volume (D, H, W), item = 1 (uint8) or 4 (uint32; the bits of an int32 are taken as they are),
+ *   0 = background.  The voxel pitch (az, ay, ax) is integers in 1 .. 16 and |o|^2 = az^2 dz^2 + ay^2 dy^2 + ax^2 dx^2.
+ *   1 <= cap <= 65535.  d2(q) is what emp_label_edt (E5) defines for that cap: 0 on background, otherwise the smallest
+ *   |q - u|^2 over the voxels u of the volume with L(u) != L(q), background included, and cap where nothing lies nearer;
+ *   positions outside the volume are no candidates.
+ * Definition.  T2(p) = max { d2(q) : q in the volume, |p - q|^2 < d2(q) }, 0 if there is no such q: the squared radius
+ *   of the largest ball, centred anywhere, that fits its object and covers p.  All quantities are exact integers and
+ *   the result does not depend on how it is computed.
+ *   - T2(p) > 0 exactly where L(p) != 0, and T2 >= d2 (q = p covers p).
+ *   - No label test is needed: every p with |p - q|^2 < d2(q) carries q's label by the definition of d2, so a ball
+ *     never leaks into a touching object, and the volume's faces do not thin an object.
+ *   - The cap is part of the definition: the result for cap is NOT min(T2 without a cap, cap).  A ball whose true
+ *     radius exceeds the cap is shrunk to the cap and covers less.  totals[1] counts the voxels with d2 == cap; when it
+ *     is 0 the result is the uncapped one.
+ *   - The diameter at p is 2 sqrt(T2(p)) in pitch units, with the voxel-centre bias of the edt: a line one voxel wide
+ *     reads 2.  Nothing corrects for it.
+ * The volume may be continued along z by two halo stacks as in E5: `below` holds hb >= 0 slices that stand for z = -hb
+ *   .. -1 and `above` ha >= 0 slices for z = D .. D + ha - 1; 0 = the volume's face.  d2 is computed over the EXTENDED
+ *   volume of hb + D + ha slices, whose end slices are faces, and T2 is written for the D slices of lab.  With h =
+ *   floor(sqrt(cap - 1)) / az, T2 of the core needs d2 on h slices per side and that d2 needs labels on h more: 2 h
+ *   slices per side make every z-partition equal the undivided volume, with no table, seam or merge.  With fewer, the
+ *   result is that of the truncated volume.
+ * The three steps share `work` (emp_label_thick_work_bytes; -1 for a shape a call would refuse): 8 bytes per voxel of
+ *   the extended volume and a few words per tile of 8 x 8 x 64 voxels.  Kernels initialise all of it.  A call covers at most
+ *   2^31 - 1 voxels, halos included; a larger block and every other argument error is refused with EMP_EINVAL before
+ *   any launch, nothing is truncated.  D == 0 is a no-op (totals are zeroed).
+ * Step 1  emp_label_thick_edt: d2 of every voxel of the extended volume, by the passes of emp_label_edt.
+ * Step 2  emp_label_thick_lists: per tile of the extended volume the voxels with d2 > 0 as keys d2 << 12 | voxel in
+ *         tile, sorted descending, at the tile's scanned offset, and the tile's largest d2.  totals (device int64[4]):
+ *         candidates listed, voxels of the core with d2 == cap, tiles with a list, longest list.
+ * Step 3  emp_label_thick_resolve: T2 of the core as (D, H, W) uint16.  A tile's values start as its own d2 and take
+ *         the balls of its own list and of every tile whose largest ball can reach it; a maximum, without global
+ *         atomics, bit-identical from run to run.                                                                    */
+int64_t emp_label_thick_work_bytes(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha);
+int emp_label_thick_edt(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, int64_t hb,
+                        const void *above, int64_t ha, int az, int ay, int ax, int cap, void *work, int64_t work_bytes,
+                        void *stream);
+int emp_label_thick_lists(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha, int cap, void *work,
+                          int64_t work_bytes, int64_t *totals, void *stream);
+int emp_label_thick_resolve(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha, int az, int ay, int ax, int cap,
+                            const void *work, int64_t work_bytes, uint16_t *out, void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
