@@ -9,6 +9,8 @@ import os
 
 import torch
 
+from .tables import bits
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libemp_hip.so')
 
@@ -363,6 +365,59 @@ def _z_blocks(slab, below, above, per):
         yield z0, z1, slab[z0:z1], below if z0 == 0 else slab[z0 - 1], above if z1 == D else slab[z1]
 
 
+def _dhw(name, slab, what="slab"):
+    if slab.dim() != 3:
+        raise ValueError(f"{name}: {what} must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+    return tuple(int(s) for s in slab.shape)
+
+
+def _z_base(name, z_base):
+    import numbers
+    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
+        raise ValueError(f"{name}: z_base must be a non-negative integer, got {z_base!r}")
+
+
+def _halo_blocks(name, D, H, W, per, halo, n_below, n_above, limit):
+    """The z-blocks [z0, z1) of `per` slices of a stage that reads `halo` slices on either side of a block, as far as
+    the slab and the caller's n_below / n_above slices go: a list, after every block with its halos has been held
+    against the `limit` of voxels per call."""
+    blocks = [(z0, min(D, z0 + per)) for z0 in range(0, D, per)]
+    for z0, z1 in blocks:
+        total = min(halo, z0 + n_below) + z1 - z0 + min(halo, D - z1 + n_above)
+        if total * H * W > limit:
+            raise ValueError(f"{name}: a block of {z1 - z0} slices of {H} x {W} with its halo slices is {total * H * W} "
+                             f"voxels, above the limit of {limit} voxels per call")
+    return blocks
+
+
+def _z_stack(slab, lo, hi, below, above):
+    """The slices [lo, hi) of a slab continued by the caller's stacks beyond its ends -- lo may be negative and hi
+    exceed D -- as far as there are any: (tensor or None, slices).  A view where one part suffices."""
+    D = int(slab.shape[0])
+    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
+    parts = []
+    if lo < 0 and n_below:
+        parts.append(below[max(n_below + lo, 0):])
+    if max(lo, 0) < min(hi, D):
+        parts.append(slab[max(lo, 0):min(hi, D)])
+    if hi > D and n_above:
+        parts.append(above[:min(hi - D, n_above)])
+    parts = [p for p in parts if p.shape[0]]
+    if not parts:
+        return None, 0
+    if len(parts) == 1:
+        return parts[0], int(parts[0].shape[0])
+    both = torch.cat([bits(p) for p in parts])
+    return both.view(slab.dtype), int(both.shape[0])
+
+
+def _one_table(tables, empty, merge):
+    """what a stage returns of its blocks' tables: `empty` for none, the table of a single block as it is, `merge` of more"""
+    if len(tables) < 2:
+        return tables[0] if tables else empty
+    return merge(tables)
+
+
 def median_harden_window(prob, ks, thr, hist=None, halo=None, want_tail=False, tail_out=None):
     """The recursive median + harden of a WINDOW of a longer stack (emp_median_harden_window).
     prob (D,C,H,W) fp32 cuda: the window's raw probabilities; hist (m,C,H,W), m = ks // 2: the filtered values of the m
@@ -680,12 +735,8 @@ def label_overlaps(gt, pred, stream=None, info=None):
             n = int(n_out.item())
             # the capacity is one row per span: keep the table only
             tables.append((pairs[:n].clone(), counts[:n].clone()))
-    if not tables:
-        return empty
-    if len(tables) == 1:
-        return tables[0]
     from .evaluation import merge_overlaps
-    return merge_overlaps(tables)
+    return _one_table(tables, empty, merge_overlaps)
 
 
 DEFLATE_MAX_BYTES = 2 ** 31 - 1      # worst-case output of one emp_deflate_count call: its segment sizes are scanned in int32
@@ -821,18 +872,14 @@ def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, in
     (measurements.merge_tables); a single slice above the limit is a ValueError.  An empty or all-zero slab gives a
     (0, 14) table.  Two host syncs per block (run count, label count).  info: a dict that receives 'blocks' (kernel
     calls made), 'runs' (runs they sorted) and 'work_bytes' (largest workspace of one call)."""
-    import numbers
     slab = _label_operand("measure_labels", "slab", slab)
-    if slab.dim() != 3:
-        raise ValueError(f"measure_labels: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw("measure_labels", slab)
     dev = slab.device
     if below is not None:
         below = _label_operand("measure_labels", "below", below, slab.dtype, (H, W), dev)
     if above is not None:
         above = _label_operand("measure_labels", "above", above, slab.dtype, (H, W), dev)
-    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
-        raise ValueError(f"measure_labels: z_base must be a non-negative integer, got {z_base!r}")
+    _z_base("measure_labels", z_base)
     block_voxels = _block_voxels("measure_labels", block_voxels, MEASURE_MAX_VOXELS)
     stats = {} if info is None else info
     stats.update(blocks=0, runs=0, work_bytes=0)
@@ -866,12 +913,8 @@ def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, in
                  _ptr(work), wb, _ptr(table), _ptr(n_out), _current_stream(), alg_bytes=rows * W * item)
             # the capacity is one row per run: keep the table only
             tables.append(table[:int(n_out.item())].clone())
-    if not tables:
-        return empty
-    if len(tables) == 1:
-        return tables[0]
     from .measurements import merge_tables
-    return merge_tables(tables)
+    return _one_table(tables, empty, merge_tables)
 
 
 COMPONENTS_MAX_VOXELS = MEASURE_MAX_VOXELS   # voxels per emp_label_components call, as for its siblings
@@ -1002,16 +1045,12 @@ def label_components(slab, connectivity=26, z_base=0, block_voxels=None, info=No
     is that of the undivided slab.  A single slice above the limit is a ValueError, as is every other argument error,
     before any GPU work.  An empty or all-zero slab gives a (0, 9) table.  Two host syncs per block.  info: a dict that
     receives 'blocks', 'runs' and 'work_bytes' (largest workspace of one call)."""
-    import numbers
     if connectivity not in (6, 18, 26) or isinstance(connectivity, bool):
         raise ValueError(f"label_components: connectivity must be 6, 18 or 26, got {connectivity!r}")
     slab = _components_operand("slab", slab, (torch.uint8, torch.int32, torch.uint32))
-    if slab.dim() != 3:
-        raise ValueError(f"label_components: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw("label_components", slab)
     dev = slab.device
-    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
-        raise ValueError(f"label_components: z_base must be a non-negative integer, got {z_base!r}")
+    _z_base("label_components", z_base)
     block_voxels = _block_voxels("label_components", block_voxels, COMPONENTS_MAX_VOXELS)
     stats = {} if info is None else info
     stats.update(blocks=0, runs=0, work_bytes=0)
@@ -1111,14 +1150,10 @@ def label_holes(slab, below=None, above=None, z_base=0, block_voxels=None, info=
     slice above the limit is a ValueError, as is every other argument error, before any GPU work.  An empty slab or one
     without a zero voxel gives a (0, 10) table.  Two host syncs per block.  info: a dict that receives 'blocks', 'runs'
     and 'work_bytes' (largest workspace of one call)."""
-    import numbers
-    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
-        raise ValueError(f"label_holes: z_base must be a non-negative integer, got {z_base!r}")
+    _z_base("label_holes", z_base)
     block_voxels = _block_voxels("label_holes", block_voxels, HOLES_MAX_VOXELS)
     slab = _label_operand("label_holes", "slab", slab)
-    if slab.dim() != 3:
-        raise ValueError(f"label_holes: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw("label_holes", slab)
     dev = slab.device
     if below is not None:
         below = _label_operand("label_holes", "below", below, slab.dtype, (H, W), dev)
@@ -1218,9 +1253,7 @@ def _morph(name, slab, sampling, bound, below, above, block_voxels, info):
     if block_voxels is not None:
         block_voxels = _label_int(name, "block_voxels", block_voxels, 1, MORPH_MAX_VOXELS)
     slab = _label_operand(name, "slab", slab)
-    if slab.dim() != 3:
-        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw(name, slab)
     dev = slab.device
     if below is not None:
         below = _label_operand(name, "below", below, slab.dtype, (None, H, W), dev)
@@ -1239,42 +1272,16 @@ def _morph(name, slab, sampling, bound, below, above, block_voxels, info):
     # block_voxels counts a block's own slices; its halo slices come on top and count towards the limit of a call
     per = max(1, MORPH_MAX_VOXELS // (H * W) - 2 * halo) if block_voxels is None else block_voxels // (H * W)
     n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
-    for z0 in range(0, D, per):
-        z1 = min(D, z0 + per)
-        total = min(halo, z0 + n_below) + z1 - z0 + min(halo, D - z1 + n_above)
-        if total * H * W > MORPH_MAX_VOXELS:
-            raise ValueError(f"{name}: a block of {z1 - z0} slices of {H} x {W} with its halo slices is {total * H * W} "
-                             f"voxels, above the limit of {MORPH_MAX_VOXELS} voxels per call")
+    blocks = _halo_blocks(name, D, H, W, per, halo, n_below, n_above, MORPH_MAX_VOXELS)
     require_gpu()
     item = slab.element_size()
     out = torch.empty((D, H, W), dtype=out_dtype, device=dev)
     near = name == 'label_dilate'
 
-    def stack(lo, hi, outer, at_start):
-        """the slices [lo, hi) of the slab continued by `outer`, the caller's stack beyond the slab's end"""
-        if at_start:                                          # lo may be negative: those come from the end of `outer`
-            inner = slab[max(lo, 0):hi]
-            want = -lo if lo < 0 else 0
-            extra = None if outer is None or want == 0 else outer[max(int(outer.shape[0]) - want, 0):]
-            parts = [p for p in (extra, inner) if p is not None and p.shape[0]]
-        else:
-            inner = slab[lo:min(hi, D)]
-            want = hi - D if hi > D else 0
-            extra = None if outer is None or want == 0 else outer[:want]
-            parts = [p for p in (inner, extra) if p is not None and p.shape[0]]
-        if not parts:
-            return None, 0
-        if len(parts) == 1:
-            return parts[0], int(parts[0].shape[0])
-        bits = [p.view(torch.int32) if p.dtype == torch.uint32 else p for p in parts]     # torch copies few uint32 tensors
-        both = torch.cat(bits)
-        return (both.view(torch.uint32) if slab.dtype == torch.uint32 else both), int(both.shape[0])
-
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
-            lo, hb = stack(z0 - halo, z0, below, True)
-            hi, ha = stack(z1, z1 + halo, above, False)
+        for z0, z1 in blocks:
+            lo, hb = _z_stack(slab, z0 - halo, z0, below, above)
+            hi, ha = _z_stack(slab, z1, z1 + halo, below, above)
             d = z1 - z0
             wb = query('emp_label_dilate_work_bytes' if near else 'emp_label_edt_work_bytes', d, H, W, hb, ha)
             if wb < 0:
@@ -1517,9 +1524,7 @@ def label_grow(slab, seeds, below=None, above=None, block_voxels=None, max_sweep
     'rounds', 'active_tiles' (listed tiles: those that hold a labelled voxel) and 'work_bytes' (state included); it
     keeps counting through resume()."""
     slab = _grow_operand("label_grow", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
-    if slab.dim() != 3:
-        raise ValueError(f"label_grow: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw("label_grow", slab)
     dev = slab.device
     seeds = _grow_operand("label_grow", "seeds", seeds, (torch.uint32, torch.int32), (D, H, W), dev)
     if block_voxels is None:
@@ -1585,9 +1590,7 @@ def label_mesh(slab, below=None, above=None, z_base=0, depth=None, top=True, blo
     'quads' and 'work_bytes' (largest workspace of one call)."""
     name = "label_mesh"
     slab = _label_operand(name, "slab", slab)
-    if slab.dim() != 3:
-        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw(name, slab)
     dev = slab.device
     if below is not None:
         below = _label_operand(name, "below", below, slab.dtype, (H, W), dev)
@@ -1786,9 +1789,7 @@ class LabelThin:
 
     def __init__(self, slab, z_base=0, block_voxels=None, info=None):
         slab = _grow_operand("label_thin", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
-        if slab.dim() != 3:
-            raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-        D, H, W = (int(s) for s in slab.shape)
+        D, H, W = _dhw("label_thin", slab)
         self.z_base = _label_int("label_thin", "z_base", z_base, 0, 2 ** 62)
         block_voxels = THIN_MAX_VOXELS if block_voxels is None else _label_int("label_thin", "block_voxels", block_voxels, 1,
                                                                                THIN_MAX_VOXELS)
@@ -1921,8 +1922,7 @@ def label_thin(slab, below=None, above=None, z_base=0, block_voxels=None, max_it
         max_iterations = _label_int("label_thin", "max_iterations", max_iterations, 1, 2 ** 62)
     if below is not None or above is not None:                    # checked before anything is allocated
         slab = _grow_operand("label_thin", "slab", slab, (torch.uint8, torch.int32, torch.uint32))
-        if slab.dim() != 3:
-            raise ValueError(f"label_thin: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
+        _dhw("label_thin", slab)
         _thin_halo(slab, "below", below), _thin_halo(slab, "above", above)
     t = LabelThin(slab, z_base, block_voxels, info)
     t._stats['voxels_deleted'] = 0
@@ -1955,9 +1955,7 @@ def label_graph(skel, below=None, above=None, z_base=0, depth=None, block_voxels
     'blocks', 'vertices', 'edges' and 'work_bytes' (largest workspace of one call)."""
     name = "label_graph"
     skel = _label_operand(name, "skel", skel)
-    if skel.dim() != 3:
-        raise ValueError(f"{name}: skel must be a (D, H, W) tensor, got {tuple(skel.shape)}")
-    D, H, W = (int(s) for s in skel.shape)
+    D, H, W = _dhw(name, skel, "skel")
     dev = skel.device
     if below is not None:
         below = _label_operand(name, "below", below, skel.dtype, (H, W), dev)
@@ -2136,7 +2134,6 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
     receives 'blocks' (z-blocks walked), 'tiles' (tiles listed), 'records' and 'work_bytes' (largest workspaces of one
     block, records included)."""
     import math
-    import numbers
     r2, sampling = _contacts_r2(r2, sampling)
     az, ay, ax = sampling
     a = _contacts_operand("a", a)
@@ -2160,8 +2157,7 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
             raise ValueError(f"label_contacts: {what} is on {t.device}: expected a tensor on the GPU")
         if t is not None and t.device != dev:
             raise ValueError(f"label_contacts: {what} is on {t.device}, a on {dev}")
-    if isinstance(z_base, bool) or not isinstance(z_base, numbers.Integral) or z_base < 0:
-        raise ValueError(f"label_contacts: z_base must be a non-negative integer, got {z_base!r}")
+    _z_base("label_contacts", z_base)
     if block_voxels is None:
         block_voxels = CONTACTS_MAX_VOXELS
     else:
@@ -2173,26 +2169,6 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
         return empty
     per = _block_slices("label_contacts", H, W, block_voxels)
     require_gpu()
-    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
-    bits = (lambda t: t.view(torch.int32)) if b.dtype == torch.uint32 else (lambda t: t)   # torch copies few uint32 tensors
-
-    def stack(lo, hi):
-        """B's slices [lo, hi), continued by the caller's stacks beyond the slab's ends: (tensor or None, slices)"""
-        parts = []
-        if lo < 0 and n_below:
-            parts.append(below[max(n_below + lo, 0):])
-        if max(lo, 0) < min(hi, D):
-            parts.append(b[max(lo, 0):min(hi, D)])
-        if hi > D and n_above:
-            parts.append(above[:min(hi - D, n_above)])
-        parts = [p for p in parts if p.shape[0]]
-        if not parts:
-            return None, 0
-        if len(parts) == 1:
-            return parts[0], int(parts[0].shape[0])
-        both = torch.cat([bits(p) for p in parts])
-        return both.view(b.dtype), int(both.shape[0])
-
     tables = []
     with torch.cuda.device(dev):
         ball = torch.from_numpy(contact_ball(r2, sampling)).to(dev)
@@ -2201,8 +2177,8 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
         while todo:
             z0, z1 = todo.pop()
             d = z1 - z0
-            lo, hb = stack(z0 - halo, z0)
-            hi, ha = stack(z1, z1 + halo)
+            lo, hb = _z_stack(b, z0 - halo, z0, below, above)
+            hi, ha = _z_stack(b, z1, z1 + halo, below, above)
             pa, pb = a[z0:z1], b[z0:z1]
             geom = (_ptr(pa), pa.element_size(), _ptr(pb), pb.element_size(), d, H, W, _ptr(lo), hb, _ptr(hi), ha,
                     1 if same else 0, az, ay, ax, r2, _ptr(ball), n_ball)
@@ -2248,39 +2224,13 @@ def label_contacts(a, b=None, r2=1, sampling=(1, 1, 1), below=None, above=None, 
                  _ptr(rwork), rb, _ptr(table), rows, _current_stream())
             stats['work_bytes'] = max(stats['work_bytes'], int(wb) + int(sb) + int(rb) + 40 * n)
             tables.append(table)
-    if not tables:
-        return empty
-    if len(tables) == 1:
-        return tables[0]
     from .contacts import merge_tables
-    return merge_tables(tables)
+    return _one_table(tables, empty, merge_tables)
 
 
 THICK_MAX_VOXELS = MEASURE_MAX_VOXELS         # voxels per emp_label_thick_* call, halos included
 THICK_BLOCK_VOXELS = 2 ** 28                 # a z-block's own voxels by default: 8 bytes of workspace per voxel
 THICK_COLUMNS = 3
-
-
-def _z_stack(slab, lo, hi, below, above):
-    """The slices [lo, hi) of a slab continued by the caller's stacks beyond its ends -- lo may be negative and hi
-    exceed D -- as far as there are any: (tensor or None, slices).  A view where one part suffices."""
-    D = int(slab.shape[0])
-    n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
-    parts = []
-    if lo < 0 and n_below:
-        parts.append(below[max(n_below + lo, 0):])
-    if max(lo, 0) < min(hi, D):
-        parts.append(slab[max(lo, 0):min(hi, D)])
-    if hi > D and n_above:
-        parts.append(above[:min(hi - D, n_above)])
-    parts = [p for p in parts if p.shape[0]]
-    if not parts:
-        return None, 0
-    if len(parts) == 1:
-        return parts[0], int(parts[0].shape[0])
-    u32 = slab.dtype == torch.uint32                                   # torch copies few uint32 tensors
-    both = torch.cat([p.view(torch.int32) if u32 else p for p in parts])
-    return (both.view(torch.uint32) if u32 else both), int(both.shape[0])
 
 
 def label_thickness(slab, cap=1024, sampling=(1, 1, 1), below=None, above=None, block_voxels=None, info=None):
@@ -2308,9 +2258,7 @@ def label_thickness(slab, cap=1024, sampling=(1, 1, 1), below=None, above=None, 
     az, ay, ax = sampling = _morph_sampling(name, sampling)
     block_voxels = _block_voxels(name, block_voxels, THICK_MAX_VOXELS) if block_voxels is not None else None
     slab = _label_operand(name, "slab", slab)
-    if slab.dim() != 3:
-        raise ValueError(f"{name}: slab must be a (D, H, W) tensor, got {tuple(slab.shape)}")
-    D, H, W = (int(s) for s in slab.shape)
+    D, H, W = _dhw(name, slab)
     dev = slab.device
     if below is not None:
         below = _label_operand(name, "below", below, slab.dtype, (None, H, W), dev)
@@ -2329,18 +2277,12 @@ def label_thickness(slab, cap=1024, sampling=(1, 1, 1), below=None, above=None, 
     else:
         per = _block_slices(name, H, W, block_voxels)
     n_below, n_above = (0 if t is None else int(t.shape[0]) for t in (below, above))
-    for z0 in range(0, D, per):
-        z1 = min(D, z0 + per)
-        total = min(halo, z0 + n_below) + z1 - z0 + min(halo, D - z1 + n_above)
-        if total * H * W > THICK_MAX_VOXELS:
-            raise ValueError(f"{name}: a block of {z1 - z0} slices of {H} x {W} with its halo slices is {total * H * W} "
-                             f"voxels, above the limit of {THICK_MAX_VOXELS} voxels per call")
+    blocks = _halo_blocks(name, D, H, W, per, halo, n_below, n_above, THICK_MAX_VOXELS)
     require_gpu()
     item = slab.element_size()
     tables = []
     with torch.cuda.device(dev):
-        for z0 in range(0, D, per):
-            z1 = min(D, z0 + per)
+        for z0, z1 in blocks:
             d = z1 - z0
             lo, hb = _z_stack(slab, z0 - halo, z0, below, above)
             hi, ha = _z_stack(slab, z1, z1 + halo, below, above)
@@ -2372,12 +2314,8 @@ def label_thickness(slab, cap=1024, sampling=(1, 1, 1), below=None, above=None, 
             stats['capped'] += capped
             stats['lists'] += lists
             stats['longest'] = max(stats['longest'], longest)
-    if not tables:
-        return t2, empty
-    if len(tables) == 1:
-        return t2, tables[0]
     from .thickness import merge_tables
-    return t2, merge_tables(tables)
+    return t2, _one_table(tables, empty, merge_tables)
 
 
 def sort_u64_i32(keys, vals, begin_bit=0, end_bit=64):

@@ -10,6 +10,8 @@ module works on O(#components) tables: joining the components of z-blocks and of
 import numpy as np
 import torch
 
+from .tables import _host, bits, merge_seamed
+
 __all__ = ['COLUMNS', 'merge_blocks', 'seam_pairs', 'plan', 'merged_table', 'split_volume']
 
 COLUMNS = ('label', 'voxels', 'first', 'z0', 'y0', 'x0', 'z1', 'y1', 'x1')
@@ -25,13 +27,6 @@ def _check_connectivity(connectivity):
     return int(connectivity)
 
 
-def _host(t):
-    """a table or pair list as an int64 numpy array"""
-    if isinstance(t, torch.Tensor):
-        t = t.cpu().numpy()
-    return np.asarray(t, dtype=np.int64)
-
-
 def _wide(t):
     """an integer plane as a non-negative int64 tensor (the bits of int32 / uint32 are taken as they are)"""
     if not isinstance(t, torch.Tensor):
@@ -39,8 +34,7 @@ def _wide(t):
         if a.dtype in (np.int32, np.uint32):
             return torch.from_numpy(np.ascontiguousarray(a).view(np.uint32).astype(np.int64))
         return torch.from_numpy(a.astype(np.int64))
-    if t.dtype == torch.uint32:
-        t = t.view(torch.int32)
+    t = bits(t)
     return t.long() & 0xffffffff if t.dtype == torch.int32 else t.long()
 
 
@@ -77,40 +71,13 @@ def merge_blocks(tables, seams, return_index=False):
     renumbered ascending by `first`, so it equals the table of the undivided volume.  Union-find on the host
     (scipy.sparse.csgraph).  numpy in, numpy out; with any tensor among the tables the result is a tensor on its
     device.  return_index: also the (n_provisional,) int64 map from p - 1 to the row of the merged table."""
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    tables = list(tables)
-    dev = next((t.device for t in tables if isinstance(t, torch.Tensor)), None)
-    parts = [_host(t).reshape(-1, len(COLUMNS)) for t in tables]
-    rows = np.concatenate(parts) if parts else np.zeros((0, len(COLUMNS)), np.int64)
-    n = len(rows)
-    pairs = [_host(s).reshape(-1, 2) for s in seams]
-    pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int64)
-    if len(pairs) and (pairs.min() < 1 or pairs.max() > n):
-        raise ValueError(f"merge_blocks: seam ids outside 1 .. {n}")
-    if len(pairs) and (rows[pairs[:, 0] - 1, 0] != rows[pairs[:, 1] - 1, 0]).any():
-        raise ValueError("merge_blocks: a seam joins components of different labels")
-    if n == 0:
-        out, index = rows, np.zeros((0,), np.int64)
-    else:
-        graph = coo_matrix((np.ones(len(pairs), np.int8), (pairs[:, 0] - 1, pairs[:, 1] - 1)), shape=(n, n))
-        m, grp = connected_components(graph, directed=False)
-        first = np.full(m, np.iinfo(np.int64).max, np.int64)
-        np.minimum.at(first, grp, rows[:, 2])
-        rank = np.empty(m, np.int64)
-        rank[np.argsort(first, kind='stable')] = np.arange(m)
-        index = rank[grp]
-        out = np.zeros((m, len(COLUMNS)), np.int64)
-        out[:, 2:6] = np.iinfo(np.int64).max
-        out[index, 0] = rows[:, 0]
-        np.add.at(out[:, 1], index, rows[:, 1])
-        for col in (2, 3, 4, 5):
-            np.minimum.at(out[:, col], index, rows[:, col])
-        for col in (6, 7, 8):
-            np.maximum.at(out[:, col], index, rows[:, col])
-    if dev is not None:
-        out, index = torch.from_numpy(out).to(dev), torch.from_numpy(index).to(dev)
-    return (out, index) if return_index else out
+    def same_label(rows, pairs):
+        if len(pairs) and (rows[pairs[:, 0] - 1, 0] != rows[pairs[:, 1] - 1, 0]).any():
+            raise ValueError("merge_blocks: a seam joins components of different labels")
+
+    # the label is the same all over a component, so its minimum is the label
+    return merge_seamed(tables, seams, len(COLUMNS), first=2, sums=[1], mins=[0, 2, 3, 4, 5], maxs=[6, 7, 8],
+                        check=same_label, return_index=return_index)
 
 
 def plan(table, min_size=None, min_span=None):

@@ -19,6 +19,9 @@ import numbers
 import numpy as np
 import torch
 
+from .morphology import check_sampling
+from .tables import _labels_to_device, gather_keyed, merge_keyed, volume_device, volume_slabs, volume_table
+
 __all__ = ['COLUMNS', 'MAX_HALO', 'check', 'halo_slices', 'merge_tables', 'gather_tables', 'volume_contacts', 'derive',
            'partners']
 
@@ -26,14 +29,6 @@ COLUMNS = ('a', 'b', 'voxels', 'min_d2', 'sum_z', 'sum_y', 'sum_x', 'faces_z', '
 MAX_HALO = 4
 _SUM = [2, 4, 5, 6, 7, 8, 9]
 _MIN = [3]
-
-
-def _check_sampling(sampling):
-    from .morphology import _check_sampling as morph_sampling
-    try:
-        return morph_sampling(sampling)
-    except ValueError as e:
-        raise ValueError(str(e).replace("morph:", "contacts:", 1)) from None
 
 
 def _radius(r, sampling):
@@ -65,7 +60,7 @@ def check(contacts):
             raise ValueError("contacts must be None, r, (r, (az, ay, ax)) or (r, (az, ay, ax), pairs), got "
                              f"{contacts!r}")
         r = contacts[0]
-        sampling = _check_sampling(contacts[1])
+        sampling = check_sampling("contacts", contacts[1])
         if len(contacts) == 3:
             raw = contacts[2]
             if isinstance(raw, (str, bytes)) or not isinstance(raw, (tuple, list)) or len(raw) == 0:
@@ -91,56 +86,14 @@ def merge_tables(tables):
     (a, b), ascending by (a, b) as unsigned 32-bit values, columns 2 and 4..9 added and column 3 the minimum.  numpy in,
     numpy out; with any torch tensor among them the result is a torch table on that tensor's device.  No tables, or empty
     ones, give a (0, 10) table.  Integer sums and minima: exact whatever the order."""
-    tables = list(tables)
-    n_col = len(COLUMNS)
-    if any(isinstance(t, torch.Tensor) for t in tables):
-        dev = next(t.device for t in tables if isinstance(t, torch.Tensor))
-        parts = [torch.as_tensor(t).to(dev).reshape(-1, n_col).long() for t in tables]
-        rows = torch.cat(parts)
-        if rows.shape[0] == 0:
-            return rows
-        # labels are below 2^32: the upper label goes to the sign bit only from 2^31 on, which the flip keeps in order
-        key = ((rows[:, 0] << 32) | rows[:, 1]) ^ (-1 << 63)
-        keys, inv = torch.unique(key, return_inverse=True)                  # ascending
-        out = torch.zeros((keys.shape[0], n_col), dtype=torch.int64, device=dev)
-        keys = keys ^ (-1 << 63)
-        out[:, 0] = (keys >> 32) & 0xffffffff
-        out[:, 1] = keys & 0xffffffff
-        out[:, _MIN] = torch.iinfo(torch.int64).max
-        for cols, how in ((_SUM, 'sum'), (_MIN, 'amin')):
-            acc = out[:, cols].contiguous()
-            acc.scatter_reduce_(0, inv[:, None].expand(-1, len(cols)), rows[:, cols].contiguous(), how)
-            out[:, cols] = acc
-        return out
-    parts = [np.asarray(t, dtype=np.int64).reshape(-1, n_col) for t in tables]
-    rows = np.concatenate(parts) if parts else np.zeros((0, n_col), np.int64)
-    if len(rows) == 0:
-        return rows
-    key = (rows[:, 0].astype(np.uint64) << np.uint64(32)) | rows[:, 1].astype(np.uint64)
-    keys, inv = np.unique(key, return_inverse=True)
-    inv = inv.reshape(-1)
-    out = np.zeros((len(keys), n_col), np.int64)
-    out[:, 0] = (keys >> np.uint64(32)).astype(np.int64)
-    out[:, 1] = (keys & np.uint64(0xffffffff)).astype(np.int64)
-    out[:, _MIN] = np.iinfo(np.int64).max
-    for c in _SUM:
-        np.add.at(out[:, c], inv, rows[:, c])
-    for c in _MIN:
-        np.minimum.at(out[:, c], inv, rows[:, c])
-    return out
+    return merge_keyed(tables, len(COLUMNS), [0, 1], _SUM, _MIN)
 
 
 def gather_tables(table, group=None):
     """The ranks' tables merged: every rank of `group` passes the table of its own slab and receives the table of all of
     them (one count all-gather + one padded all-gather, as measurements.gather_tables).  Without an initialised process
     group the table comes back merged with itself, i.e. sorted."""
-    from .inference import sharded
-    if sharded._world(group)[1] == 1:
-        return merge_tables([table])
-    was_numpy = not isinstance(table, torch.Tensor)
-    t = torch.as_tensor(table).reshape(-1, len(COLUMNS)).long()
-    merged = merge_tables(sharded._gather_var(t, group))
-    return merged.cpu().numpy() if was_numpy else merged
+    return gather_keyed(table, len(COLUMNS), merge_tables, group)
 
 
 def volume_contacts(a, b=None, *, r, sampling=(1, 1, 1), slab_rows=None, group=None):
@@ -154,28 +107,16 @@ def volume_contacts(a, b=None, *, r, sampling=(1, 1, 1), slab_rows=None, group=N
     volume must hand each slab B's halo themselves (_hip.label_contacts' below / above, as infer_volume does) and then
     call gather_tables."""
     from . import _hip
-    from .evaluation import _SLAB_VOXELS, _labels_to_device
-    sampling = _check_sampling(sampling)
+    sampling = check_sampling("contacts", sampling)
     r2 = _radius(r, sampling)
     if len(a.shape) != 3:
         raise ValueError(f"volume_contacts: a must be (D, H, W), got {tuple(a.shape)}")
     if b is not None and tuple(b.shape) != tuple(a.shape):
         raise ValueError(f"volume_contacts: b is {tuple(b.shape)}, a is {tuple(a.shape)}")
     _hip.require_gpu()
-    on_dev = all(isinstance(t, torch.Tensor) and t.is_cuda for t in (a, b) if t is not None)
-    dev = a.device if on_dev else torch.device('cuda', torch.cuda.current_device())
-    n = int(a.shape[0])
-    if slab_rows is None:
-        per_row = int(np.prod(a.shape[1:], dtype=np.int64))
-        slab_rows = max(n, 1) if on_dev else max(1, _SLAB_VOXELS // max(per_row, 1))
-    elif isinstance(slab_rows, bool) or not isinstance(slab_rows, (int, np.integer)) or slab_rows < 1:
-        raise ValueError(f"volume_contacts: slab_rows must be a positive number of slices, got {slab_rows!r}")
-    slab_rows = int(slab_rows)
-    halo = halo_slices(r2, sampling)
+    dev, resident = volume_device(a, b)
     tables = []
-    for z in range(0, n, slab_rows):
-        z1 = min(n, z + slab_rows)
-        lo, hi = max(0, z - halo), min(n, z1 + halo)
+    for z, z1, lo, hi in volume_slabs("volume_contacts", a.shape, slab_rows, resident, halo_slices(r2, sampling)):
         # one upload covers B's slab and its halo on both sides; A's slab is a view of it in the same-volume case
         ext = _labels_to_device((a if b is None else b)[lo:hi], dev)
         ext = ext if ext.is_contiguous() else ext.contiguous()
@@ -191,8 +132,7 @@ def volume_contacts(a, b=None, *, r, sampling=(1, 1, 1), slab_rows=None, group=N
                 tables.append(_hip.label_contacts(slab, core, r2, sampling, below=below, above=above, z_base=z))
                 del slab
         del ext, core, below, above
-    table = merge_tables(tables) if tables else torch.zeros((0, len(COLUMNS)), dtype=torch.int64, device=dev)
-    return gather_tables(table, group).cpu().numpy()
+    return volume_table(tables, len(COLUMNS), merge_tables, gather_tables, group, dev)
 
 
 def derive(table, sampling=(1, 1, 1), unit=1.0):

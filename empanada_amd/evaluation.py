@@ -13,6 +13,8 @@ import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 
+from .tables import _SLAB_VOXELS, _labels_to_device, gather_keyed, merge_keyed, volume_slabs, volume_table  # noqa: F401
+
 __all__ = ['panoptic_quality', 'volume_pq', 'merge_overlaps', 'gather_overlaps', 'scores_from_overlaps', 'volume_overlaps',
            'volume_scores', 'f1', 'ap', 'precision', 'recall', 'f1_50', 'f1_75', 'precision_50',
            'precision_75', 'recall_50', 'recall_75', 'iou', 'Evaluator']
@@ -188,8 +190,29 @@ class Evaluator:
 
 
 # ----------------------------------------------------------------------------- scores from the sparse overlap table
-def _is_torch(tables):
-    return any(isinstance(x, torch.Tensor) for t in tables for x in t)
+def _table(pairs, counts):
+    """(pairs, counts) as one (n, 3) int64 table; a tensor, on its device, if either is one"""
+    dev = next((x.device for x in (pairs, counts) if isinstance(x, torch.Tensor)), None)
+    if dev is None:
+        return np.concatenate([np.asarray(pairs, dtype=np.int64).reshape(-1, 2),
+                               np.asarray(counts, dtype=np.int64).reshape(-1, 1)], axis=1)
+    return torch.cat([torch.as_tensor(pairs).to(dev).reshape(-1, 2).long(),
+                      torch.as_tensor(counts).to(dev).reshape(-1, 1).long()], dim=1)
+
+
+def _merge3(tables):
+    return merge_keyed(tables, 3, [0, 1], [2])
+
+
+def _gather3(table, group):
+    return gather_keyed(table, 3, _merge3, group)
+
+
+def _split(table):
+    """an (n, 3) table as (pairs, counts), each contiguous"""
+    if isinstance(table, torch.Tensor):
+        return table[:, :2].contiguous(), table[:, 2].contiguous()
+    return np.ascontiguousarray(table[:, :2]), np.ascontiguousarray(table[:, 2])
 
 
 def merge_overlaps(tables):
@@ -197,42 +220,14 @@ def merge_overlaps(tables):
     ranks' shares -- and the result is one such table with every distinct pair once, its counts added, ascending by
     (gt label, pred label).  numpy in, numpy out; with any torch tensor among them the result is a torch table on that
     tensor's device.  Integer sums: exact whatever the order."""
-    tables = [(p, c) for p, c in tables]
-    if _is_torch(tables):
-        dev = next(x.device for t in tables for x in t if isinstance(x, torch.Tensor))
-        pairs = [torch.as_tensor(p).to(dev).reshape(-1, 2).long() for p, _ in tables]
-        counts = [torch.as_tensor(c).to(dev).reshape(-1).long() for _, c in tables]
-        pairs = torch.cat(pairs) if pairs else torch.zeros((0, 2), dtype=torch.int64, device=dev)
-        counts = torch.cat(counts) if counts else torch.zeros((0,), dtype=torch.int64, device=dev)
-        if pairs.shape[0] == 0:
-            return pairs, counts
-        uniq, inv = torch.unique(pairs, dim=0, return_inverse=True)      # rows in lexicographic order
-        return uniq, torch.zeros((uniq.shape[0],), dtype=torch.int64, device=dev).index_add_(0, inv.reshape(-1), counts)
-    pairs = [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p, _ in tables]
-    counts = [np.asarray(c, dtype=np.int64).reshape(-1) for _, c in tables]
-    pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int64)
-    counts = np.concatenate(counts) if counts else np.zeros((0,), np.int64)
-    if len(pairs) == 0:
-        return pairs, counts
-    order = np.lexsort((pairs[:, 1], pairs[:, 0]))
-    pairs, counts = pairs[order], counts[order]
-    head = np.concatenate([[True], np.any(pairs[1:] != pairs[:-1], axis=1)])
-    return pairs[head], np.add.reduceat(counts, np.flatnonzero(head))
+    return _split(_merge3([_table(p, c) for p, c in tables]))
 
 
 def gather_overlaps(pairs, counts, group=None):
     """The ranks' overlap tables added up: every rank of `group` passes its own table and receives the table of all of
     them (one count all-gather + one padded all-gather, as the run tables travel in inference/sharded.py).  Without an
     initialised process group the table comes back merged with itself, i.e. sorted."""
-    from .inference import sharded
-    if sharded._world(group)[1] == 1:
-        return merge_overlaps([(pairs, counts)])
-    was_numpy = not isinstance(pairs, torch.Tensor)
-    p = torch.as_tensor(pairs).reshape(-1, 2).long()
-    c = torch.as_tensor(counts).reshape(-1).long().to(p.device)
-    parts = sharded._gather_var(torch.cat([p, c[:, None]], dim=1), group)
-    pairs, counts = merge_overlaps([(t[:, :2], t[:, 2]) for t in parts])
-    return (pairs.cpu().numpy(), counts.cpu().numpy()) if was_numpy else (pairs, counts)
+    return _split(_gather3(_table(pairs, counts), group))
 
 
 def _match_components(gi, pi, iou, n_g):
@@ -323,36 +318,6 @@ def scores_from_overlaps(pairs, counts, iou_thr=0.5, instances=True, return_inst
     return (scores, match) if return_instances else scores
 
 
-_SLAB_VOXELS = 1 << 27        # host volumes are uploaded in slabs of about this many voxels (512 MiB of uint32)
-
-
-def _labels_to_device(x, dev):
-    """one slab of labels as a contiguous uint8 or uint32 tensor on `dev`; any integer type whose values fit 32 bits"""
-    if isinstance(x, torch.Tensor):
-        if x.dtype == torch.bool:
-            x = x.to(torch.uint8)
-        if x.dtype not in (torch.uint8, torch.int32, torch.uint32):
-            if x.is_floating_point() or x.is_complex():
-                raise ValueError(f"volume_scores: labels must be integers, got {x.dtype}")
-            x = x.to(torch.int64)
-            if x.numel() and (int(x.min()) < 0 or int(x.max()) >= 2 ** 32):
-                raise ValueError("volume_scores: labels must lie in 0 .. 2^32 - 1")
-            x = x.to(torch.int32)                                       # keeps the low 32 bits
-        return x.to(dev).contiguous()
-    a = np.asarray(x)
-    if a.dtype == np.bool_:
-        a = a.astype(np.uint8)
-    if a.dtype.kind not in 'iu':
-        raise ValueError(f"volume_scores: labels must be integers, got {a.dtype}")
-    if a.dtype == np.uint8:
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    if a.dtype != np.uint32:
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32):
-            raise ValueError("volume_scores: labels must lie in 0 .. 2^32 - 1")
-        a = a.astype(np.uint32)
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(dev).view(torch.uint32)
-
-
 def volume_overlaps(gt, pred, *, slab_rows=None, group=None):
     """The overlap table of two label volumes of equal shape as a numpy (pairs, counts): `gt` and `pred` are numpy
     arrays, tensors or anything that has a shape and can be sliced along axis 0 (a ZarrV2Array, say).  Every slab of
@@ -370,24 +335,14 @@ def volume_overlaps(gt, pred, *, slab_rows=None, group=None):
     if len(set(on_dev)) > 1:
         raise ValueError(f"volume_scores: gt and pred are on different devices ({on_dev[0]}, {on_dev[1]})")
     dev = on_dev[0] if on_dev else torch.device('cuda', torch.cuda.current_device())
-    n = int(gt.shape[0])
-    if slab_rows is None:
-        per_row = int(np.prod(gt.shape[1:], dtype=np.int64))
-        slab_rows = max(n, 1) if len(on_dev) == 2 else max(1, _SLAB_VOXELS // max(per_row, 1))
-    elif isinstance(slab_rows, bool) or not isinstance(slab_rows, (int, np.integer)) or slab_rows < 1:
-        raise ValueError(f"volume_scores: slab_rows must be a positive number of indices along axis 0, got {slab_rows!r}")
+    slabs = volume_slabs("volume_scores", gt.shape, slab_rows, len(on_dev) == 2, what="indices along axis 0")
     tables = []
-    for z in range(0, n, int(slab_rows)):
-        g = _labels_to_device(gt[z:z + slab_rows], dev)
-        p = _labels_to_device(pred[z:z + slab_rows], dev)
-        tables.append(_hip.label_overlaps(g, p))
+    for z, z1, _, _ in slabs:
+        g = _labels_to_device(gt[z:z1], dev)
+        p = _labels_to_device(pred[z:z1], dev)
+        tables.append(_table(*_hip.label_overlaps(g, p)))
         del g, p
-    if tables:
-        pairs, counts = merge_overlaps(tables)
-    else:
-        pairs, counts = torch.zeros((0, 2), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev)
-    pairs, counts = gather_overlaps(pairs, counts, group)
-    return pairs.cpu().numpy(), counts.cpu().numpy()
+    return _split(volume_table(tables, 3, _merge3, _gather3, group, dev))
 
 
 def volume_scores(gt, pred, *, instances=True, iou_thr=0.5, slab_rows=None, group=None):

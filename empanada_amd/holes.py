@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .components import _host, seam_pairs
+from .tables import bits, merge_seamed
 
 __all__ = ['COLUMNS', 'NO_LABEL', 'merge_blocks', 'plan', 'fill_volume']
 
@@ -28,46 +29,18 @@ def merge_blocks(tables, seams, return_index=False):
     renumbered ascending by `first`, so it equals the table of the undivided volume.  Union-find on the host
     (scipy.sparse.csgraph).  numpy in, numpy out; with any tensor among the tables the result is a tensor on its
     device.  return_index: also the (n_provisional,) int64 map from p - 1 to the row of the merged table."""
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    tables = list(tables)
-    dev = next((t.device for t in tables if isinstance(t, torch.Tensor)), None)
-    parts = [_host(t).reshape(-1, len(COLUMNS)) for t in tables]
-    rows = np.concatenate(parts) if parts else np.zeros((0, len(COLUMNS)), np.int64)
-    n = len(rows)
-    pairs = [_host(s).reshape(-1, 2) for s in seams]
-    pairs = np.concatenate(pairs) if pairs else np.zeros((0, 2), np.int64)
-    if len(pairs) and (pairs.min() < 1 or pairs.max() > n):
-        raise ValueError(f"merge_blocks: seam ids outside 1 .. {n}")
-    if n == 0:
-        out, index = rows, np.zeros((0,), np.int64)
-    else:
-        graph = coo_matrix((np.ones(len(pairs), np.int8), (pairs[:, 0] - 1, pairs[:, 1] - 1)), shape=(n, n))
-        m, grp = connected_components(graph, directed=False)
-        first = np.full(m, np.iinfo(np.int64).max, np.int64)
-        np.minimum.at(first, grp, rows[:, 1])
-        rank = np.empty(m, np.int64)
-        rank[np.argsort(first, kind='stable')] = np.arange(m)
-        index = rank[grp]
-        out = np.zeros((m, len(COLUMNS)), np.int64)
-        out[:, 1:5] = np.iinfo(np.int64).max
-        out[:, 8] = NO_LABEL
-        np.add.at(out[:, 0], index, rows[:, 0])
-        for col in (1, 2, 3, 4, 8):
-            np.minimum.at(out[:, col], index, rows[:, col])
-        for col in (5, 6, 7, 9):
-            np.maximum.at(out[:, col], index, rows[:, col])
-        border = np.zeros(m, bool)
-        border[index[rows[:, 9] == 0]] = True
-        out[border, 8], out[border, 9] = NO_LABEL, 0
-    if dev is not None:
-        out, index = torch.from_numpy(out).to(dev), torch.from_numpy(index).to(dev)
-    return (out, index) if return_index else out
+    def border(rows, index, out):
+        hit = np.zeros(len(out), bool)
+        hit[index[rows[:, 9] == 0]] = True
+        out[hit, 8], out[hit, 9] = NO_LABEL, 0
+
+    return merge_seamed(tables, seams, len(COLUMNS), first=1, sums=[0], mins=[1, 2, 3, 4, 8], maxs=[5, 6, 7, 9],
+                        fixup=border, return_index=return_index)
 
 
 def _is_zero(plane):
     """the zero voxels of an integer plane as a bool tensor (torch compares few uint32 tensors)"""
-    return (plane.view(torch.int32) if plane.dtype == torch.uint32 else plane) == 0
+    return bits(plane) == 0
 
 
 def _check_cap(max_voxels, what='max_voxels'):

@@ -10,6 +10,9 @@ tables of the z-blocks of a volume -- each measured with its true neighbour slic
 import numpy as np
 import torch
 
+from .tables import (_labels_to_device, bits, gather_keyed, merge_keyed, volume_device, volume_slabs,
+                     volume_table)
+
 __all__ = ['COLUMNS', 'merge_tables', 'gather_tables', 'volume_measurements', 'derive']
 
 COLUMNS = ('label', 'voxels', 'z0', 'y0', 'x0', 'z1', 'y1', 'x1', 'sum_z', 'sum_y', 'sum_x',
@@ -24,54 +27,14 @@ def merge_tables(tables):
     distinct label, ascending by label, columns 1 and 8..13 added, 2..4 the minimum and 5..7 the maximum.  numpy in,
     numpy out; with any torch tensor among them the result is a torch table on that tensor's device.  No tables, or
     empty ones, give a (0, 14) table.  Integer sums, minima and maxima: exact whatever the order."""
-    tables = list(tables)
-    n_col = len(COLUMNS)
-    if any(isinstance(t, torch.Tensor) for t in tables):
-        dev = next(t.device for t in tables if isinstance(t, torch.Tensor))
-        parts = [torch.as_tensor(t).to(dev).reshape(-1, n_col).long() for t in tables]
-        rows = torch.cat(parts)
-        if rows.shape[0] == 0:
-            return rows
-        labels, inv = torch.unique(rows[:, 0], return_inverse=True)         # ascending
-        out = torch.zeros((labels.shape[0], n_col), dtype=torch.int64, device=dev)
-        out[:, 0] = labels
-        out[:, _MIN] = torch.iinfo(torch.int64).max
-        out[:, _MAX] = torch.iinfo(torch.int64).min
-        for cols, how in ((_SUM, 'sum'), (_MIN, 'amin'), (_MAX, 'amax')):
-            acc = out[:, cols].contiguous()
-            acc.scatter_reduce_(0, inv[:, None].expand(-1, len(cols)), rows[:, cols].contiguous(), how)
-            out[:, cols] = acc
-        return out
-    parts = [np.asarray(t, dtype=np.int64).reshape(-1, n_col) for t in tables]
-    rows = np.concatenate(parts) if parts else np.zeros((0, n_col), np.int64)
-    if len(rows) == 0:
-        return rows
-    labels, inv = np.unique(rows[:, 0], return_inverse=True)
-    inv = inv.reshape(-1)
-    out = np.zeros((len(labels), n_col), np.int64)
-    out[:, 0] = labels
-    out[:, _MIN] = np.iinfo(np.int64).max
-    out[:, _MAX] = np.iinfo(np.int64).min
-    for c in _SUM:
-        np.add.at(out[:, c], inv, rows[:, c])
-    for c in _MIN:
-        np.minimum.at(out[:, c], inv, rows[:, c])
-    for c in _MAX:
-        np.maximum.at(out[:, c], inv, rows[:, c])
-    return out
+    return merge_keyed(tables, len(COLUMNS), [0], _SUM, _MIN, _MAX)
 
 
 def gather_tables(table, group=None):
     """The ranks' tables merged: every rank of `group` passes the table of its own slab and receives the table of all of
     them (one count all-gather + one padded all-gather, as the overlap tables travel in evaluation.gather_overlaps).
     Without an initialised process group the table comes back merged with itself, i.e. sorted."""
-    from .inference import sharded
-    if sharded._world(group)[1] == 1:
-        return merge_tables([table])
-    was_numpy = not isinstance(table, torch.Tensor)
-    t = torch.as_tensor(table).reshape(-1, len(COLUMNS)).long()
-    merged = merge_tables(sharded._gather_var(t, group))
-    return merged.cpu().numpy() if was_numpy else merged
+    return gather_keyed(table, len(COLUMNS), merge_tables, group)
 
 
 def volume_measurements(labels, *, slab_rows=None, group=None):
@@ -84,33 +47,22 @@ def volume_measurements(labels, *, slab_rows=None, group=None):
     z-slabs of ONE volume must hand each slab its neighbour slices themselves (_hip.measure_labels' below / above, as
     infer_volume does) and then call gather_tables."""
     from . import _hip
-    from .evaluation import _SLAB_VOXELS, _labels_to_device
     _hip.require_gpu()
     if len(labels.shape) != 3:
         raise ValueError(f"volume_measurements: labels must be (D, H, W), got {tuple(labels.shape)}")
-    on_dev = isinstance(labels, torch.Tensor) and labels.is_cuda
-    dev = labels.device if on_dev else torch.device('cuda', torch.cuda.current_device())
-    n = int(labels.shape[0])
-    if slab_rows is None:
-        per_row = int(np.prod(labels.shape[1:], dtype=np.int64))
-        slab_rows = max(n, 1) if on_dev else max(1, _SLAB_VOXELS // max(per_row, 1))
-    elif isinstance(slab_rows, bool) or not isinstance(slab_rows, (int, np.integer)) or slab_rows < 1:
-        raise ValueError(f"volume_measurements: slab_rows must be a positive number of slices, got {slab_rows!r}")
-    slab_rows = int(slab_rows)
+    dev, resident = volume_device(labels)
     tables, below = [], None
-    for z in range(0, n, slab_rows):
+    for z, z1, _, hi in volume_slabs("volume_measurements", labels.shape, slab_rows, resident, halo=1):
         # one upload covers the slab and the slice above it; the slice below is kept from the slab before
-        z1 = min(n, z + slab_rows)
-        part = _labels_to_device(labels[z:min(n, z1 + 1)], dev)
+        part = _labels_to_device(labels[z:hi], dev)
         slab = part[:z1 - z]
-        above = part[z1 - z] if z1 < n else None
+        above = part[z1 - z] if hi > z1 else None
         if slab.numel():
             tables.append(_hip.measure_labels(slab, below=below, above=above, z_base=z))
         if slab.shape[0]:                   # a copy of one slice, so that the slab itself can go (as int32: same bits)
-            below = slab[-1].view(torch.int32).clone().view(torch.uint32) if slab.dtype == torch.uint32 else slab[-1].clone()
+            below = bits(slab[-1]).clone().view(slab.dtype)
         del part, slab, above
-    table = merge_tables(tables) if tables else torch.zeros((0, len(COLUMNS)), dtype=torch.int64, device=dev)
-    return gather_tables(table, group).cpu().numpy()
+    return volume_table(tables, len(COLUMNS), merge_tables, gather_tables, group, dev)
 
 
 def derive(table, spacing=(1.0, 1.0, 1.0)):

@@ -19,21 +19,71 @@ import numbers
 import numpy as np
 import torch
 
-__all__ = ['OPS', 'check', 'halo_slices', 'morph_volume']
+from .tables import bits
+
+__all__ = ['OPS', 'check', 'check_sampling', 'check_radius', 'check_cap', 'halo_slices', 'morph_volume']
 
 OPS = ('erode', 'dilate', 'open', 'close')
 R2_MAX = 65534
 
 
-def _check_sampling(sampling):
+def check_sampling(who, sampling):
+    """a voxel pitch (az, ay, ax), three integers in 1 .. 16, for the reader `who`"""
     try:
         vals = tuple(sampling)
     except TypeError:
         vals = None
     if vals is None or len(vals) != 3 or any(isinstance(a, (bool, np.bool_)) or not isinstance(a, numbers.Integral)
                                              or not 1 <= a <= 16 for a in vals):
-        raise ValueError(f"morph: the sampling must be three integers (az, ay, ax) in 1 .. 16, got {sampling!r}")
+        raise ValueError(f"{who}: the sampling must be three integers (az, ay, ax) in 1 .. 16, got {sampling!r}")
     return tuple(int(a) for a in vals)
+
+
+def _is_real(r):
+    return not isinstance(r, (bool, np.bool_)) and isinstance(r, numbers.Real) and math.isfinite(r)
+
+
+def check_radius(who, r, sampling=(1, 1, 1)):
+    """A real radius r in the units of the sampling -> (r2, sampling) for the reader `who`: r2 = floor(r^2 + 1e-9) must
+    lie in min(sampling)^2 .. 65534.  The sampling is read once r is known to be a positive real number."""
+    if not _is_real(r) or r <= 0:
+        raise ValueError(f"{who}: the radius must be a positive real number, got {r!r}")
+    sampling = check_sampling(who, sampling)
+    r = float(r)
+    if r * r > R2_MAX + 1:
+        raise ValueError(f"{who}: the radius {r!r} is above sqrt({R2_MAX})")
+    r2 = int(math.floor(r * r + 1e-9))
+    if r2 > R2_MAX:
+        raise ValueError(f"{who}: the radius {r!r} is above sqrt({R2_MAX})")
+    if r2 < min(sampling) ** 2:
+        raise ValueError(f"{who}: the radius {r!r} is below the smallest pitch of {sampling}: the ball is a point")
+    return r2, sampling
+
+
+def check_cap(who, arg, r_default, at_least=None, cap_max=65535):
+    """infer_volume's `skeleton` / `thickness` argument -> None or (r_cap, cap, sampling) for the reader `who`.  arg:
+    None, True (r_default, sampling (1, 1, 1)), r_cap, or (r_cap, (az, ay, ax)).  r_cap is a real number >= at_least
+    (None: any positive one) and cap = floor(r_cap^2 + 1e-9), as check_radius reads a radius, must lie in 1 .. cap_max."""
+    if arg is None:
+        return None
+    sampling = (1, 1, 1)
+    if arg is True:
+        r = r_default
+    elif isinstance(arg, (tuple, list)):
+        if len(arg) != 2:
+            raise ValueError(f"{who} must be None, True, r_cap or (r_cap, (az, ay, ax)), got {arg!r}")
+        r = arg[0]
+        sampling = check_sampling(who, arg[1])
+    else:
+        r = arg
+    if not _is_real(r) or (r <= 0 if at_least is None else r < at_least):
+        raise ValueError(f"{who}: r_cap must be a " + ("positive real number" if at_least is None else
+                                                        f"real number >= {at_least}") + f", got {r!r}")
+    r = float(r)
+    cap = int(math.floor(r * r + 1e-9)) if r * r <= cap_max + 1 else cap_max + 1
+    if not 1 <= cap <= cap_max:
+        raise ValueError(f"{who}: r_cap = {r!r} gives cap = r_cap^2 outside 1 .. {cap_max}")
+    return r, cap, sampling
 
 
 def check(morph):
@@ -45,21 +95,10 @@ def check(morph):
         return None
     if not isinstance(morph, (tuple, list)) or len(morph) not in (2, 3):
         raise ValueError(f"morph must be None, (op, r) or (op, r, (az, ay, ax)), got {morph!r}")
-    op, r = morph[0], morph[1]
+    op = morph[0]
     if not isinstance(op, str) or op not in OPS:
         raise ValueError(f"morph: the operation must be one of {OPS}, got {op!r}")
-    if isinstance(r, (bool, np.bool_)) or not isinstance(r, numbers.Real) or not math.isfinite(r) or r <= 0:
-        raise ValueError(f"morph: the radius must be a positive real number, got {r!r}")
-    sampling = _check_sampling(morph[2]) if len(morph) == 3 else (1, 1, 1)
-    r = float(r)
-    if r * r > R2_MAX + 1:
-        raise ValueError(f"morph: the radius {r!r} is above sqrt({R2_MAX})")
-    r2 = int(math.floor(r * r + 1e-9))
-    if r2 > R2_MAX:
-        raise ValueError(f"morph: the radius {r!r} is above sqrt({R2_MAX})")
-    if r2 < min(sampling) ** 2:
-        raise ValueError(f"morph: the radius {r!r} is below the smallest pitch of {sampling}: the ball is a point")
-    return op, r2, sampling
+    return (op,) + check_radius("morph", *morph[1:])
 
 
 def halo_slices(op, r2, sampling=(1, 1, 1)):
@@ -67,11 +106,6 @@ def halo_slices(op, r2, sampling=(1, 1, 1)):
     that for the compound operations"""
     one = math.isqrt(int(r2)) // int(sampling[0])
     return one if op in ('erode', 'dilate') else 2 * one
-
-
-def _bits(t):
-    """torch compares and copies few uint32 tensors"""
-    return t.view(torch.int32) if t.dtype == torch.uint32 else t
 
 
 def morph_volume(slab, shape3d, op, r2, sampling=(1, 1, 1), group=None, z_base=0):
@@ -87,7 +121,7 @@ def morph_volume(slab, shape3d, op, r2, sampling=(1, 1, 1), group=None, z_base=0
     from .inference import sharded
     if op not in OPS:
         raise ValueError(f"morph_volume: the operation must be one of {OPS}, got {op!r}")
-    sampling = _check_sampling(sampling)
+    sampling = check_sampling("morph", sampling)
     if len(shape3d) != 3 or any(int(s) < 0 for s in shape3d):
         raise ValueError(f"morph_volume: shape3d must be (D, H, W), got {shape3d!r}")
     r2 = int(r2)
@@ -98,15 +132,15 @@ def morph_volume(slab, shape3d, op, r2, sampling=(1, 1, 1), group=None, z_base=0
         new = _hip.label_dilate(slab, r2, sampling, below=below, above=above)
     else:
         parts = [p for p in (below, slab, above) if p is not None]
-        ext = slab if len(parts) == 1 else torch.cat([_bits(p) for p in parts]).view(slab.dtype)
+        ext = slab if len(parts) == 1 else torch.cat([bits(p) for p in parts]).view(slab.dtype)
         lo = 0 if below is None else int(below.shape[0])
         first, second = (_hip.label_erode, _hip.label_dilate) if op == 'open' else (_hip.label_dilate, _hip.label_erode)
         new = second(first(ext, r2, sampling), r2, sampling)[lo:lo + int(slab.shape[0])]
         if op == 'close':
-            new = torch.where(_bits(slab) != 0, _bits(slab), _bits(new)).view(slab.dtype)
+            new = torch.where(bits(slab) != 0, bits(slab), bits(new)).view(slab.dtype)
         new = new.contiguous()
     # an erosion or an opening only takes voxels and a dilation or a closing only gives them: two counts say how many
-    change = int(torch.count_nonzero(_bits(new))) - int(torch.count_nonzero(_bits(slab)))
+    change = int(torch.count_nonzero(bits(new))) - int(torch.count_nonzero(bits(slab)))
     assert change <= 0 if op in ('erode', 'open') else change >= 0
     moved = np.asarray([max(-change, 0), max(change, 0)], np.int64)
     moved = sharded._all_reduce_sum(moved, group)

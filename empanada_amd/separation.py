@@ -35,16 +35,12 @@ def check(separate):
     if isinstance(separate, (tuple, list)):
         if len(separate) not in (2, 3):
             raise ValueError(f"separate must be None, r, (r, min_core) or (r, min_core, (az, ay, ax)), got {separate!r}")
-        r, min_core = separate[0], _check_min_core(separate[1])
-        erosion = ('erode', r) + tuple(separate[2:])
+        r, min_core, pitch = separate[0], _check_min_core(separate[1]), tuple(separate[2:])
     else:
-        r, min_core, erosion = separate, 1, ('erode', separate)
+        r, min_core, pitch = separate, 1, ()
     if isinstance(r, (str, bytes)):
         raise ValueError(f"separate must be None, r, (r, min_core) or (r, min_core, (az, ay, ax)), got {separate!r}")
-    try:
-        _, r2, sampling = morphology.check(erosion)
-    except ValueError as e:
-        raise ValueError(str(e).replace('morph', 'separate', 1)) from None
+    r2, sampling = morphology.check_radius("separate", r, *pitch)
     return r2, min_core, sampling
 
 
@@ -138,7 +134,7 @@ def separate_volume(slab, shape3d, r2, min_core=1, sampling=(1, 1, 1), connectiv
     from . import _hip, components, morphology
     from .inference import sharded
     from .measurements import gather_tables
-    sampling = morphology._check_sampling(sampling)
+    sampling = morphology.check_sampling("morph", sampling)
     min_core = _check_min_core(min_core)
     connectivity = components._check_connectivity(connectivity)
     if len(shape3d) != 3 or any(int(s) < 0 for s in shape3d):

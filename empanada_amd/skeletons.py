@@ -20,9 +20,6 @@ idempotent -- thinning a skeleton again eats its curves from their ends.
 Not built: pruning of short branches, SWC / neuroglancer precomputed skeletons, surface (2-D isthmus) skeletons and
 anisotropic thinning (the sampling is used for the radius only; the thinning is on the voxel lattice).
 """
-import math
-import numbers
-
 import numpy as np
 
 __all__ = ['OBJECT_COLUMNS', 'R_CAP', 'check', 'thin_volume', 'skeleton_volume', 'derive', 'object_skeleton',
@@ -38,29 +35,8 @@ def check(skeleton):
     (1, 1, 1)), r_cap, or (r_cap, (az, ay, ax)).  r_cap is the largest radius reported, a positive real in the units of
     the sampling, read as morphology.check reads a radius: cap = floor(r_cap^2 + 1e-9) must lie in 1 .. 65535.  The
     sampling is three integers in 1 .. 16.  Everything else is a ValueError."""
-    from .morphology import _check_sampling
-    if skeleton is None:
-        return None
-    sampling = (1, 1, 1)
-    if skeleton is True:
-        r = R_CAP
-    elif isinstance(skeleton, (tuple, list)):
-        if len(skeleton) != 2:
-            raise ValueError(f"skeleton must be None, True, r_cap or (r_cap, (az, ay, ax)), got {skeleton!r}")
-        r = skeleton[0]
-        try:
-            sampling = _check_sampling(skeleton[1])
-        except ValueError as e:
-            raise ValueError(str(e).replace("morph:", "skeleton:", 1)) from None
-    else:
-        r = skeleton
-    if isinstance(r, (bool, np.bool_)) or not isinstance(r, numbers.Real) or not math.isfinite(r) or r <= 0:
-        raise ValueError(f"skeleton: r_cap must be a positive real number, got {r!r}")
-    r = float(r)
-    cap = int(math.floor(r * r + 1e-9)) if r * r <= CAP_MAX + 1 else CAP_MAX + 1
-    if not 1 <= cap <= CAP_MAX:
-        raise ValueError(f"skeleton: r_cap = {r!r} gives cap = r_cap^2 outside 1 .. {CAP_MAX}")
-    return r, cap, sampling
+    from .morphology import check_cap
+    return check_cap("skeleton", skeleton, R_CAP, cap_max=CAP_MAX)
 
 
 def thin_volume(slab, group=None, z_base=0, info=None):

@@ -20,10 +20,11 @@ Not built: a masked or calibrated thickness that removes the voxel bias, thickne
 radii above sqrt(65535), compressed output of the uint16 map, a pyramid of the map.
 """
 import math
-import numbers
 
 import numpy as np
 import torch
+
+from .tables import _labels_to_device, gather_keyed, merge_keyed, volume_device, volume_slabs, volume_table
 
 __all__ = ['COLUMNS', 'R_CAP', 'check', 'halo_slices', 'merge_tables', 'gather_tables', 'thickness_volume', 'derive',
            'histogram', 'volume_thickness']
@@ -38,29 +39,8 @@ def check(thickness):
     (1, 1, 1)), r_cap, or (r_cap, (az, ay, ax)).  r_cap is the largest radius reported, a real number >= 1 in the units
     of the sampling, read as skeletons.check reads it: cap = floor(r_cap^2 + 1e-9) must lie in 1 .. 65535.  The sampling
     is three integers in 1 .. 16.  Everything else is a ValueError."""
-    from .morphology import _check_sampling
-    if thickness is None:
-        return None
-    sampling = (1, 1, 1)
-    if thickness is True:
-        r = R_CAP
-    elif isinstance(thickness, (tuple, list)):
-        if len(thickness) != 2:
-            raise ValueError(f"thickness must be None, True, r_cap or (r_cap, (az, ay, ax)), got {thickness!r}")
-        r = thickness[0]
-        try:
-            sampling = _check_sampling(thickness[1])
-        except ValueError as e:
-            raise ValueError(str(e).replace("morph:", "thickness:", 1)) from None
-    else:
-        r = thickness
-    if isinstance(r, (bool, np.bool_)) or not isinstance(r, numbers.Real) or not math.isfinite(r) or r < 1:
-        raise ValueError(f"thickness: r_cap must be a real number >= 1, got {r!r}")
-    r = float(r)
-    cap = int(math.floor(r * r + 1e-9)) if r * r <= CAP_MAX + 1 else CAP_MAX + 1
-    if not 1 <= cap <= CAP_MAX:
-        raise ValueError(f"thickness: r_cap = {r!r} gives cap = r_cap^2 outside 1 .. {CAP_MAX}")
-    return r, cap, sampling
+    from .morphology import check_cap
+    return check_cap("thickness", thickness, R_CAP, at_least=1, cap_max=CAP_MAX)
 
 
 def halo_slices(cap, sampling=(1, 1, 1)):
@@ -74,46 +54,14 @@ def merge_tables(tables):
     (label, t2), ascending by (label, t2) with the label as an unsigned 32-bit value, the voxels added.  numpy in, numpy
     out; with any torch tensor among them the result is a torch table on that tensor's device.  No tables, or empty
     ones, give a (0, 3) table."""
-    tables = list(tables)
-    n_col = len(COLUMNS)
-    if any(isinstance(t, torch.Tensor) for t in tables):
-        dev = next(t.device for t in tables if isinstance(t, torch.Tensor))
-        rows = torch.cat([torch.as_tensor(t).to(dev).reshape(-1, n_col).long() for t in tables])
-        if rows.shape[0] == 0:
-            return rows
-        # labels are below 2^32: the label reaches the sign bit only from 2^31 on, which the flip keeps in order
-        key = ((rows[:, 0] << 32) | rows[:, 1]) ^ (-1 << 63)
-        keys, inv = torch.unique(key, return_inverse=True)                  # ascending
-        out = torch.zeros((keys.shape[0], n_col), dtype=torch.int64, device=dev)
-        keys = keys ^ (-1 << 63)
-        out[:, 0] = (keys >> 32) & 0xffffffff
-        out[:, 1] = keys & 0xffffffff
-        out[:, 2] = torch.zeros_like(keys).scatter_add_(0, inv.reshape(-1), rows[:, 2].contiguous())
-        return out
-    parts = [np.asarray(t, dtype=np.int64).reshape(-1, n_col) for t in tables]
-    rows = np.concatenate(parts) if parts else np.zeros((0, n_col), np.int64)
-    if len(rows) == 0:
-        return rows
-    key = (rows[:, 0].astype(np.uint64) << np.uint64(32)) | rows[:, 1].astype(np.uint64)
-    keys, inv = np.unique(key, return_inverse=True)
-    out = np.zeros((len(keys), n_col), np.int64)
-    out[:, 0] = (keys >> np.uint64(32)).astype(np.int64)
-    out[:, 1] = (keys & np.uint64(0xffffffff)).astype(np.int64)
-    np.add.at(out[:, 2], inv.reshape(-1), rows[:, 2])
-    return out
+    return merge_keyed(tables, len(COLUMNS), [0, 1], [2])
 
 
 def gather_tables(table, group=None):
     """The ranks' tables merged: every rank of `group` passes the table of its own slab and receives the table of all of
     them (one count all-gather + one padded all-gather, as contacts.gather_tables).  Without an initialised process
     group the table comes back merged with itself, i.e. sorted."""
-    from .inference import sharded
-    if sharded._world(group)[1] == 1:
-        return merge_tables([table])
-    was_numpy = not isinstance(table, torch.Tensor)
-    t = torch.as_tensor(table).reshape(-1, len(COLUMNS)).long()
-    merged = merge_tables(sharded._gather_var(t, group))
-    return merged.cpu().numpy() if was_numpy else merged
+    return gather_keyed(table, len(COLUMNS), merge_tables, group)
 
 
 def thickness_volume(slab, group=None, cap=R_CAP * R_CAP, sampling=(1, 1, 1), info=None):
@@ -210,7 +158,6 @@ def volume_thickness(labels, *, r_cap=R_CAP, sampling=(1, 1, 1), slab_rows=None,
     the tables and capped are merged too: every rank passes a volume of its own; ranks that hold the z-slabs of ONE
     volume call thickness_volume instead."""
     from . import _hip
-    from .evaluation import _SLAB_VOXELS, _labels_to_device
     from .inference import sharded
     _, cap, sampling = check((r_cap, sampling))
     if len(labels.shape) != 3:
@@ -219,20 +166,10 @@ def volume_thickness(labels, *, r_cap=R_CAP, sampling=(1, 1, 1), slab_rows=None,
     if out is not None and tuple(out.shape) != shape:
         raise ValueError(f"volume_thickness: out is {tuple(out.shape)}, labels {shape}")
     _hip.require_gpu()
-    on_dev = isinstance(labels, torch.Tensor) and labels.is_cuda
-    dev = labels.device if on_dev else torch.device('cuda', torch.cuda.current_device())
-    n = shape[0]
-    if slab_rows is None:
-        slab_rows = max(n, 1) if on_dev else max(1, _SLAB_VOXELS // max(shape[1] * shape[2], 1))
-    elif isinstance(slab_rows, bool) or not isinstance(slab_rows, (int, np.integer)) or slab_rows < 1:
-        raise ValueError(f"volume_thickness: slab_rows must be a positive number of slices, got {slab_rows!r}")
-    slab_rows = int(slab_rows)
-    halo = halo_slices(cap, sampling)
+    dev, resident = volume_device(labels)
     t2 = np.zeros(shape, np.uint16) if out is None else out
     tables, capped = [], 0
-    for z in range(0, n, slab_rows):
-        z1 = min(n, z + slab_rows)
-        lo, hi = max(0, z - halo), min(n, z1 + halo)
+    for z, z1, lo, hi in volume_slabs("volume_thickness", shape, slab_rows, resident, halo_slices(cap, sampling)):
         ext = _labels_to_device(labels[lo:hi], dev)             # one upload covers the slab and its halo on both sides
         core = ext[z - lo:z1 - lo]
         if core.numel():
@@ -243,6 +180,5 @@ def volume_thickness(labels, *, r_cap=R_CAP, sampling=(1, 1, 1), slab_rows=None,
             tables.append(table)
             capped += stats['capped']
         del ext, core
-    table = merge_tables(tables) if tables else torch.zeros((0, len(COLUMNS)), dtype=torch.int64, device=dev)
     capped = int(sharded._all_reduce_sum(np.asarray([capped], np.int64), group)[0])
-    return t2, gather_tables(table, group).cpu().numpy(), capped
+    return t2, volume_table(tables, len(COLUMNS), merge_tables, gather_tables, group, dev), capped
