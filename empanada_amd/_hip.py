@@ -41,6 +41,10 @@ SIGNATURES = {
     'emp_upsample_bilinear': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     'emp_conv_bn_act_proj_nhwc': (_I, [_P, _P, _P, _P, _I] + [_I] * 10 + [_P, _I, _P, _P, _L, _P]),
     'emp_conv_k_slab': (_I, [_L, _I, _I, _I]),
+    'emp_conv_stream_eligible': (_I, [_I, _L] + [_I] * 9),
+    'emp_conv_stream_walk': (_I, [_L, _I, _I, _I, _L, _P, _P]),
+    'emp_conv_stream_grid': (_I, [_L, _I]),
+    'emp_conv_stream_launches': (_L, []),
     'emp_conv_k_slab_cin': (_I, [_L, _I, _I, _I, _I]),
     'emp_conv_k_slab_geom': (_I, [_L, _I, _I, _I, _I, _I, _I, _I, _I]),
     'emp_conv1x1_ws_eligible': (_I, [_L, _I, _I, _I, _I, _I, _I, _I]),

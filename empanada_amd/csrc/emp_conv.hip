@@ -614,6 +614,46 @@ extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_eligible(int ba
 extern "C" __attribute__((visibility("hidden"))) int emp_gemm_ws_launch(const float *A, const float *B, int batch, int64_t M, int N, int K, float *C,
                                                                         void *stream);
 
+// D4c (emp_conv_stream.hip): the persistent tile-stream form of the tiled kernel for its GEMM-shaped launches -- 1x1,
+// stride 1, no padding, no residual, relu in {0, 1}, Cout a multiple of 128, and a plan that says K-slab 16, LDS-direct,
+// 128-wide tiles -- from CS_MIN_TOTAL tiles on (8/3 for each of the 768 resident blocks: the smallest launches measured,
+// profiles/conv_stream.md).  Same summation order, same epilogue arithmetic: emp_conv_k_slab* keep their answers.  The
+// weight-stationary kernels keep their shapes: the launchers ask this after them, and the query answers 0 for a
+// geometry emp_conv1x1_ws_kind / emp_gemm_ws_eligible name.
+// proj != 0 (emp_conv_bn_act_proj_nhwc): not built, always 0.  EMP_CONV_NO_STREAM=1: experiments only, forces the
+// one-tile-per-block kernel; EMP_CONV_STREAM_MIN_TILES=n: experiments only, the minimum becomes n tiles per block.
+#define CS_MIN_TOTAL 2048
+extern "C" __attribute__((visibility("hidden"))) int emp_conv_stream_launch(const float *x, const float *w, const float *scale, const float *shift,
+                                                                            int relu, int batch, int64_t M, int Cin, int Cout,
+                                                                            int64_t x_bs, int64_t w_bs, int64_t out_bs, float *out,
+                                                                            int64_t out_ps, void *stream);
+extern "C" int emp_conv_stream_grid(int64_t tiles, int batch);
+
+extern "C" int emp_conv_stream_eligible(int batch, int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu,
+                                        int has_residual, int proj)
+{
+    static const char *off = getenv("EMP_CONV_NO_STREAM");
+    const char *mint = getenv("EMP_CONV_STREAM_MIN_TILES");    // read per call: tests set it for single launches
+    if (off && off[0] == '1') return 0;
+    if (proj || has_residual || batch < 1 || M <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0 && (relu == 0 || relu == 1))) return 0;
+    if (Cout % 128 != 0 || Cin % 16 != 0) return 0;
+    CgPlan pl;
+    if (batch > 1) {                                   // emp_gemm_nt_batched
+        if (Cin % CG_BK != 0) return 0;
+        pl = cg_plan(M, Cout, batch, false, true);
+        if (emp_gemm_ws_eligible(batch, M, Cout, Cin, pl.slab)) return 0;
+    } else {
+        pl = cg_plan(M, Cout, 1, false, true, true, Cin);
+        if (emp_conv1x1_ws_kind(M, Cin, Cout, KH, KW, stride, pad, relu, 0) != 0) return 0;
+    }
+    if (!(pl.slab == 16 && pl.glds && !pl.narrow && !pl.respf)) return 0;
+    const int64_t total = (int64_t)pl.tiles_m * pl.tiles_n * batch;
+    const int64_t min_total = mint ? atoll(mint) * emp_conv_stream_grid(total, 1) : CS_MIN_TOTAL;
+    if (total >= (1LL << 28) || total < min_total) return 0;
+    return 1;
+}
+
 extern "C" int emp_conv_k_slab_geom(int64_t M, int Cout, int has_residual, int Cin, int KH, int KW, int stride, int pad,
                                     int relu)
 {
@@ -663,6 +703,9 @@ extern "C" int emp_conv_bn_act_nhwc(const float *x, const float *w_okkc, const f
         res_pixel_stride < (1 << 24) && out_pixel_stride < (1 << 24))   // (its lane offsets are 32-bit)
         return emp_conv1x1_ws_launch(3, x, w_okkc, scale, shift, residual, res_pixel_stride, relu, g.M, Cin, Cout, out,
                                      out_pixel_stride, stream);
+    if (io_vec_ok && scale && shift && !residual &&
+        emp_conv_stream_eligible(1, g.M, Cin, Cout, KH, KW, stride, pad, relu, 0, 0))
+        return emp_conv_stream_launch(x, w_okkc, scale, shift, relu, 1, g.M, Cin, Cout, 0, 0, 0, out, out_pixel_stride, stream);
     const bool narrow = pl.narrow, respf = pl.respf, bk16 = pl.slab == 16;
     EMP_REQUIRE((int64_t)pl.tiles_m * pl.tiles_n < (1LL << 28), "conv: too many tiles");
     g.tiles_m = pl.tiles_m;
@@ -965,6 +1008,8 @@ extern "C" int emp_gemm_nt_batched(const float *A, const float *B, int batch, in
     const CgPlan pl = cg_plan(M, N, batch, false, true);
     if ((reinterpret_cast<uintptr_t>(C) & 15) == 0 && emp_gemm_ws_eligible(batch, M, N, K, pl.slab))
         return emp_gemm_ws_launch(A, B, batch, M, N, K, C, stream);       // short K: weight-stationary, same order
+    if ((reinterpret_cast<uintptr_t>(C) & 15) == 0 && emp_conv_stream_eligible(batch, M, K, N, 1, 1, 1, 0, 0, 0, 0))
+        return emp_conv_stream_launch(A, B, nullptr, nullptr, 0, batch, M, K, N, g.x_bs, g.w_bs, g.out_bs, C, N, stream);
     const bool narrow = pl.narrow, bk16 = pl.slab == 16;
     g.tiles_m = pl.tiles_m;
     g.tiles_n = pl.tiles_n;

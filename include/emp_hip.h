@@ -160,6 +160,24 @@ int emp_conv1x1_ws_kind_for(int64_t M, int Cin, int Cout, int KH, int KW, int st
  * another kind): the dispatch also depends on alignment, pixel strides and the tiled plan, which the queries above do
  * not see, so this is how a test tells which kernel a call took. */
 int64_t emp_conv1x1_ws_launches(int kind);
+/* D4c: the GEMM-shaped launches of the tiled kernel (1x1, stride 1, no padding, no residual, relu in {0, 1}, Cout a
+ * multiple of 128, plan: K-slab 16 and 128-wide tiles; emp_conv_bn_act_nhwc with scale AND shift, and emp_gemm_nt_batched)
+ * run on a persistent form of it (emp_conv_stream.hip) once the launch has at least 2 048 tiles of 128 x 128 (8/3 for
+ * each of its 768 resident blocks, three per CU): a block walks a sequence of tiles with one slab stream across them and
+ * stores from the accumulators.  Same summation order and epilogue arithmetic, so the result does not depend on which
+ * kernel ran and emp_conv_k_slab* answer as before.  emp_conv_stream_eligible: 1 = a launch of that geometry takes it,
+ * given 16-byte-aligned operands and pixel strides that are multiples of 4 (batch > 1: emp_gemm_nt_batched with M rows,
+ * K = Cin, N = Cout; proj != 0: emp_conv_bn_act_proj_nhwc, never eligible); 0 for the geometries of the
+ * weight-stationary kernels.  EMP_CONV_NO_STREAM=1 in the environment turns it off (experiments: A/B).
+ * emp_conv_stream_grid: blocks of a launch of batch x tiles tiles.  emp_conv_stream_walk: 1 and the (entry, tile) --
+ * tile = pixel tile * cout tiles + cout tile -- block `block` of `grid` blocks works on in its step `step`, 0 when
+ * the block has no such step; block b only visits tiles of the contiguous eighth of the sequence that XCD b & 7 owns.
+ * emp_conv_stream_launches: launches of the persistent kernel so far in this process.                            */
+int emp_conv_stream_eligible(int batch, int64_t M, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu,
+                             int has_residual, int proj);
+int emp_conv_stream_grid(int64_t tiles, int batch);
+int emp_conv_stream_walk(int64_t tiles, int batch, int grid, int block, int64_t step, int64_t *entry, int64_t *tile);
+int64_t emp_conv_stream_launches(void);
 /* relu == 2 selects the squeeze-excite gate epilogue (SqueezeExcite.forward, empanada/models/blocks.py:35-50:
  * x * sigmoid(conv(s) + bias)): out = residual * (1 / (1 + expf(-(acc * scale + shift)))), residual = the gated
  * tensor x (required); the division and the product are separate fp32 roundings, expf is the device library's;
