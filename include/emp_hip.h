@@ -121,8 +121,9 @@ int emp_upsample_bilinear(const float *x, int N, int C, int h, int w, const int6
  * bit-for-bit an fmaf chain): taps in raster order; per tap, slabs of S channels ascending; per slab the order
  * c, c + S/2 for c = 0..S/2-1; taps outside the image enter as x = 0.  S = emp_conv_k_slab(M = N*OH*OW,
  * Cout, 1, residual != NULL): 16 (three resident blocks per CU) when the launch has more than 512 blocks and does
- * not use the residual-prefetch variant, else 32.  The epilogue's multiply and adds are separate
- * fp32 roundings, as in emp_bn_act_nhwc.
+ * not use the residual-prefetch variant, else 32.  has_residual means a residual the kernel can PREFETCH (16-byte
+ * aligned, pixel stride a multiple of 4): a launch whose residual is not sums in the slab of has_residual = 0.  The
+ * epilogue's multiply and adds are separate fp32 roundings, as in emp_bn_act_nhwc.
  * x: (N, H, W, Cin), Cin % 16 == 0; w_okkc: (Cout, KH, KW, Cin) (the Conv2d weight permuted); residual and out
  * are addressed as base + pixel * pixel_stride + co (stride 0 means Cout), so out may be a channel slice of a
  * wider NHWC concat buffer.  x and w 16-byte aligned; out must not alias x.                                    */
