@@ -247,7 +247,14 @@ int emp_gconv3x3_bn_act_nhwc(const float *x, int64_t x_pixel_stride, const float
  * 3. emp_wino_output_transform: Y = A^T M A per tile, A^T = [1 1 1 0; 0 1 -1 -1], rows first
  *    (s_0 = (m_0 + m_1) + m_2, s_1 = (m_1 - m_2) - m_3), then columns likewise; then the epilogue of
  *    emp_bn_act_nhwc (scale, shift optional) and the scatter to out (N,H,W,Cout), pixel stride out_pixel_stride
- *    (0 means Cout).                                                                                          */
+ *    (0 means Cout).
+ * Alignment.  The transforms move float4: C / Cout % 4 == 0; x, V, Mw, scale, shift and out 16-byte aligned and
+ *    out_pixel_stride % 4 == 0 -- unlike emp_conv_bn_act_nhwc there is no scalar store path, so a channel slice that
+ *    starts at a channel that is no multiple of 4, or lies in a buffer whose width is none, is refused (EMP_EINVAL,
+ *    nothing launched).  The same holds for the output transforms of D5b and D5c.
+ *    emp_gemm_nt_batched asks 16 bytes of A and B only (K % 32 == 0): with a C that is not 16-byte aligned, or N % 4
+ *    != 0, the tiled kernel stores scalars (such a C is never handed to the weight-stationary or the persistent
+ *    kernel); the sums and their order are the same.                                                          */
 int emp_wino_input_transform(const float *x, int N, int H, int W, int C, int dil, const int32_t *tiles,
                              int64_t T, float *V, void *stream);
 int emp_gemm_nt_batched(const float *A, const float *B, int batch, int64_t M, int N, int K, float *C,

@@ -1,7 +1,9 @@
 """Python restatement of the tile / K-slab selection of the tiled fp32 convolution (cg_plan and emp_conv_splitk_plan in
 empanada_amd/csrc/emp_conv.hip).  The library exports the K-slab and the split count but no query for the tile width
 or the residual prefetch, so the tests that aim at one variant of conv_igemm_f32_kernel state the plan they expect
-through this mirror; tests/test_conv_plan_host.py keeps the mirror honest against the exported queries."""
+through this mirror; tests/test_conv_plan_host.py keeps the mirror honest against the exported queries.  The second half
+restates which kernel emp_gemm_nt_batched hands a batched launch to (weight-stationary, persistent stream or tiled) and
+holds the launches of the Winograd and batched-GEMM branch tests."""
 from collections import namedtuple
 
 BM = 128                   # CG_BM: output pixels per block tile
@@ -81,3 +83,71 @@ def splitk_plan(M, Cout, Cin, KH, KW):
     S = KH * KW * (Cin // 32)
     k = min(256 // tiles, S // 4, 32)
     return k if k >= 2 else 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# emp_gemm_nt_batched (batch > 1: the Winograd position GEMMs) and the fused F(2x2) loader emp_wino_gemm_fused
+
+WS_MIN_ROWS = 262144       # PW_MIN_ROWS_PLAN of emp_conv1x1.hip: batch x M rows from which the weight-stationary kernel takes a GEMM
+WS_TILE_ROWS = 32          # PW_ROWS: it takes no entry shorter than one of its row tiles
+STREAM_MIN_TILES = 2048    # CS_MIN_TOTAL of emp_conv.hip
+
+GemmRoute = namedtuple('GemmRoute', 'route narrow slab blocks')
+
+
+def gemm_route(batch, M, K, N):
+    """which kernel emp_gemm_nt_batched gives a (batch, M, K) x (batch, N, K)^T launch with a 16-byte aligned C, and the
+    plan it sums in: cg_plan at batch > 1, emp_gemm_ws_eligible, then the batch > 1 arm of emp_conv_stream_eligible.  A C
+    that is not 16-byte aligned is 'tiled' whatever this says, in the same plan."""
+    assert batch > 1 and K % 32 == 0
+    p = conv_plan(M, N, 32, batch)
+    ws = K in (64, 128) and N in (64, 128) and p.slab == 16 and M >= WS_TILE_ROWS and batch * M >= WS_MIN_ROWS
+    stream = (not ws and N % 128 == 0 and p.slab == 16 and not p.narrow
+              and STREAM_MIN_TILES <= p.blocks < (1 << 28))
+    return GemmRoute('ws' if ws else 'stream' if stream else 'tiled', p.narrow, p.slab, p.blocks)
+
+
+def wino_route(Cout):
+    """the fused F(2x2) loader has a width rule of its own and one K-slab: (narrow, slab)"""
+    return Cout <= 64, 32
+
+
+def wino_tile_count(N, H, W, dil, m):
+    """tiles of empanada_amd._hip.wino_tiles: per image, min(dil, H) x min(dil, W) sub-grids cut into m x m tiles"""
+    rows = sum(cdiv(cdiv(H - r, dil), m) for r in range(min(dil, H)))
+    cols = sum(cdiv(cdiv(W - r, dil), m) for r in range(min(dil, W)))
+    return N * rows * cols
+
+
+WINO_M = (2, 3, 4)         # F(m x m, 3x3): 16, 25 and 36 position GEMMs
+WinoCase = namedtuple('WinoCase', 'N H W Cin Cout dil T plans fused_narrow')
+
+# The launches of tests/test_wino_branches_gpu.py.  T: tiles at m = 2, 3, 4; plans: (narrow, slab) of the batched GEMM
+# of the three-call path at m = 2, 3, 4 -- every one of them the tiled kernel's; fused_narrow: the tile width of the fused
+# F(2x2) loader.
+_W16, _W32, _N16, _N32 = (False, 16), (False, 32), (True, 16), (True, 32)
+WINO_CASES = {
+    # dilated, many tile rows, both wide slabs
+    'P': WinoCase(1, 96, 100, 32, 256, 2, (2400, 1088, 624), (_W16, _W32, _W32), False),
+    # 56 couts past Cout in the last 128-wide tile; the fused loader is wide with masked B rows
+    'Q': WinoCase(1, 120, 124, 32, 200, 1, (3720, 1680, 930), (_W16, _W16, _W16), False),
+    # three 64-wide tiles, 60 masked couts, dilation 3
+    'R': WinoCase(1, 90, 94, 32, 132, 3, (2160, 990, 576), (_N16, _N16, _N16), False),
+    # dilation > H and W: every off-centre tap outside the image, one-pixel sub-grids; two images
+    'S': WinoCase(2, 3, 5, 32, 36, 7, (30, 30, 30), (_N32, _N32, _N32), True),
+    # one pixel, the smallest Cout
+    'T1': WinoCase(1, 1, 1, 32, 4, 1, (1, 1, 1), (_N32, _N32, _N32), True),
+    # one column; the fused loader is narrow
+    'C1': WinoCase(1, 13, 1, 64, 64, 2, (7, 5, 4), (_N32, _N32, _N32), True),
+}
+
+# (batch, M, K, N) -> (route, narrow, slab) of direct emp_gemm_nt_batched launches (tests/test_gemm_branches_gpu.py)
+GEMM_CASES = {
+    (16, 1100, 32, 256): ('tiled', False, 32),      # 288 blocks
+    (36, 1030, 64, 256): ('tiled', False, 16),      # 648 blocks, below the stream minimum
+    (25, 1500, 32, 200): ('tiled', False, 16),      # N % 128 = 72: 56 masked couts
+    (16, 2100, 32, 132): ('tiled', True, 16),       # the narrow plan at slab 16
+    (36, 300, 96, 40): ('tiled', True, 32),         # three slabs
+    (3, 5000, 32, 384): ('tiled', False, 32),       # three cout tiles
+    (16, 700, 32, 38): ('tiled', True, 32),         # N % 4 != 0: the scalar epilogue for every column
+}
