@@ -171,6 +171,9 @@ SIGNATURES = {
     'emp_label_thick_edt': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
     'emp_label_thick_lists': (_I, [_L, _L, _L, _L, _L, _I, _P, _L, _P, _P]),
     'emp_label_thick_resolve': (_I, [_L, _L, _L, _L, _L, _I, _I, _I, _I, _P, _L, _P, _P]),
+    'emp_label_shape_work_bytes': (_L, [_L]),
+    'emp_label_shape_labels': (_I, [_P, _I, _L, _L, _L, _P, _L, _P, _L, _P, _P, _P]),
+    'emp_label_shape': (_I, [_P, _I, _L, _L, _L, _P, _P, _L, _P, _L, _P, _P, _P]),
     'emp_mesh_neighbours': (_I, [_P, _L, _P, _L, _P, _P]),
     'emp_mesh_smooth': (_I, [_P, _P, _L, _F, _P, _P]),
     'emp_track_work_elems': (_L, [_L]),
@@ -918,6 +921,77 @@ def measure_labels(slab, below=None, above=None, z_base=0, block_voxels=None, in
             # the capacity is one row per run: keep the table only
             tables.append(table[:int(n_out.item())].clone())
     from .measurements import merge_tables
+    return _one_table(tables, empty, merge_tables)
+
+
+SHAPE_MAX_VOXELS = MEASURE_MAX_VOXELS        # voxels per emp_label_shape call, as for its siblings
+SHAPE_MAX_INDEX = 2 ** 20                    # z_base + D, H and W: the second-order sums are shifted in 64 bits
+SHAPE_COLUMNS = 26
+
+
+def shape_labels(slab, below=None, above=None, z_base=0, block_voxels=None, info=None):
+    """Shape sums of a label slab (emp_label_shape; the definition is in include/emp_hip.h, E11): an (n, 26) int64
+    table on the slab's device, one row per distinct non-zero label, ascending by label -- label, voxels, the three
+    first-order and six second-order index sums, the intercept ends along the 13 lattice directions, and the lattice
+    corners and edges the label owns (shapes.COLUMNS).  Operands, z-blocks (each with its true neighbour slices and its
+    own z_base) and the merge on the device (shapes.merge_tables) are measure_labels'; in addition z_base + D, H and W
+    must not exceed 2^20.  An empty or all-zero slab gives a (0, 26) table.  Three host syncs per block (run count,
+    label count, counters).  info: a dict that receives 'blocks' (kernel calls made), 'tiles' (tiles of 8 x 8 x 64
+    voxels that held a label), 'spilled' (voxels whose sums bypassed the tile's table in LDS because the tile held more
+    labels than it has slots; which ones do may differ from run to run, the table never does) and 'work_bytes'
+    (largest workspace of one call)."""
+    slab = _label_operand("shape_labels", "slab", slab)
+    D, H, W = _dhw("shape_labels", slab)
+    dev = slab.device
+    if below is not None:
+        below = _label_operand("shape_labels", "below", below, slab.dtype, (H, W), dev)
+    if above is not None:
+        above = _label_operand("shape_labels", "above", above, slab.dtype, (H, W), dev)
+    _z_base("shape_labels", z_base)
+    if int(z_base) + D > SHAPE_MAX_INDEX or H > SHAPE_MAX_INDEX or W > SHAPE_MAX_INDEX:
+        raise ValueError(f"shape_labels: z_base + D = {int(z_base) + D}, H = {H}, W = {W}: every index must stay below "
+                         f"{SHAPE_MAX_INDEX}")
+    block_voxels = _block_voxels("shape_labels", block_voxels, SHAPE_MAX_VOXELS)
+    stats = {} if info is None else info
+    stats.update(blocks=0, tiles=0, spilled=0, work_bytes=0)
+    empty = torch.zeros((0, SHAPE_COLUMNS), dtype=torch.int64, device=dev)
+    if slab.numel() == 0:
+        return empty
+    per = _block_slices("shape_labels", H, W, block_voxels)
+    require_gpu()
+    item = slab.element_size()
+    tables = []
+    with torch.cuda.device(dev):
+        for z0, z1, part, lo, hi in _z_blocks(slab, below, above, per):
+            d = z1 - z0
+            rows = d * H
+            wb = query('emp_label_measure_count_work_bytes', rows)
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            offs = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+            call('emp_label_measure_count', _ptr(part), item, d, H, W, _ptr(work), wb, _ptr(offs), _current_stream(),
+                 alg_bytes=rows * W * item)
+            n_runs = int(offs[-1].item())
+            stats['blocks'] += 1
+            if n_runs == 0:
+                continue
+            wb = query('emp_label_shape_work_bytes', n_runs)
+            stats['work_bytes'] = max(stats['work_bytes'], int(wb))
+            work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+            labels = torch.empty((n_runs,), dtype=torch.int32, device=dev)
+            n_out = torch.empty((1,), dtype=torch.int32, device=dev)
+            call('emp_label_shape_labels', _ptr(part), item, d, H, W, _ptr(offs), n_runs, _ptr(work), wb, _ptr(labels),
+                 _ptr(n_out), _current_stream(), alg_bytes=rows * W * item)
+            n = int(n_out.item())
+            del work
+            table = torch.empty((n, SHAPE_COLUMNS), dtype=torch.int64, device=dev)
+            counters = torch.empty((2,), dtype=torch.int64, device=dev)
+            call('emp_label_shape', _ptr(part), item, d, H, W, _ptr(lo), _ptr(hi), int(z_base) + z0, _ptr(labels), n,
+                 _ptr(table), _ptr(counters), _current_stream(), alg_bytes=rows * W * item)
+            tiles, spilled = counters.tolist()
+            stats['tiles'] += int(tiles)
+            stats['spilled'] += int(spilled)
+            tables.append(table)
+    from .shapes import merge_tables
     return _one_table(tables, empty, merge_tables)
 
 

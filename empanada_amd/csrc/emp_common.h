@@ -216,6 +216,28 @@ static inline bool emp_tiles_shape_ok(int64_t D, int64_t H, int64_t W)
     return D >= 0 && H > 0 && W > 0 && H <= 0x7fffffffLL / W && (D == 0 || H * W <= 0x7fffffffLL / D);
 }
 
+// The 26 neighbours of a voxel as one mask (include/emp_hip.h, E8), for emp_label_thin.hip and emp_label_shape.hip:
+// position p = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) of the 3 x 3 x 3 block; bit n = p, minus 1 past the centre (p = 13)
+static constexpr int lt_pos(int n) { return n < 13 ? n : n + 1; }
+static constexpr int lt_abs(int a) { return a < 0 ? -a : a; }
+static constexpr int lt_dz(int n) { return lt_pos(n) / 9 - 1; }
+static constexpr int lt_dy(int n) { return (lt_pos(n) / 3) % 3 - 1; }
+static constexpr int lt_dx(int n) { return lt_pos(n) % 3 - 1; }
+#ifdef __HIPCC__
+// the label at (z, y, x), z in -1 .. D: the slab, its two neighbour slices where there are any, 0 everywhere else
+template <typename T>
+__device__ __forceinline__ uint32_t lt_label_at(const T *__restrict__ lab, const T *__restrict__ below,
+                                                const T *__restrict__ above, int64_t D, int64_t H, int64_t W, int64_t z,
+                                                int64_t y, int64_t x)
+{
+    if (y < 0 || y >= H || x < 0 || x >= W) return 0;
+    if (z >= 0 && z < D) return (uint32_t)lab[(z * H + y) * W + x];
+    if (z == -1 && below) return (uint32_t)below[y * W + x];
+    if (z == D && above) return (uint32_t)above[y * W + x];
+    return 0;
+}
+#endif
+
 // emp_label_morph.hip: emp_label_edt's three passes with EVERY slice of the extended volume (hb + D + ha slices) as
 // output: d2[ze] is the distance inside that volume, whose first and last slices are faces.  d2 and tmp hold one uint16
 // per voxel of the extended volume each; the shape must have passed the checks of emp_label_edt_work_bytes.

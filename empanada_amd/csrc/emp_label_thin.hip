@@ -45,12 +45,7 @@
 typedef unsigned long long lt_u64;
 
 // ------------------------------------------------------------------------------------------ the predicate
-// position p = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) of the 3 x 3 x 3 block; bit n = p, minus 1 past the centre (p = 13)
-static constexpr int lt_pos(int n) { return n < 13 ? n : n + 1; }
-static constexpr int lt_abs(int a) { return a < 0 ? -a : a; }
-static constexpr int lt_dz(int n) { return lt_pos(n) / 9 - 1; }
-static constexpr int lt_dy(int n) { return (lt_pos(n) / 3) % 3 - 1; }
-static constexpr int lt_dx(int n) { return lt_pos(n) % 3 - 1; }
+// the numbering of the 3 x 3 x 3 block (lt_pos, lt_dz, lt_dy, lt_dx) is emp_common.h's
 static constexpr int lt_norm1(int n) { return lt_abs(lt_dz(n)) + lt_abs(lt_dy(n)) + lt_abs(lt_dx(n)); }
 // the positions 26-adjacent to n: they differ from it by at most 1 in every coordinate
 static constexpr uint32_t lt_adj26(int n)
@@ -494,18 +489,6 @@ extern "C" int emp_label_thin_paint(const uint8_t *state, const void *lab, int i
 // neighbourhood mask -- and its degree is the mask's population.  Positions are prefix sums: rows 0 .. R - 1 of
 // row_offsets count vertices, rows R .. 2 R - 1 edges.
 #define LG2_MAX_VOXELS (1LL << 26)            // 1 vertex and 13 edges per voxel at most: the int32 scan stays exact
-
-template <typename T>
-__device__ __forceinline__ uint32_t lt_label_at(const T *__restrict__ lab, const T *__restrict__ below,
-                                                const T *__restrict__ above, int64_t D, int64_t H, int64_t W, int64_t z,
-                                                int64_t y, int64_t x)
-{
-    if (y < 0 || y >= H || x < 0 || x >= W) return 0;
-    if (z >= 0 && z < D) return (uint32_t)lab[(z * H + y) * W + x];
-    if (z == -1 && below) return (uint32_t)below[y * W + x];
-    if (z == D && above) return (uint32_t)above[y * W + x];
-    return 0;
-}
 
 struct LtGraphOut {
     uint64_t *vkeys;    // label << 32 | global voxel number, in voxel order

@@ -447,6 +447,41 @@ def _measured(res, spacing, labels, class_names, out, group):
     return res
 
 
+def _check_shapes(shapes):
+    """infer_volume's `shapes` argument -> None or the voxel spacing (sz, sy, sx), before any GPU work"""
+    from ..shapes import check
+    return check(shapes)
+
+
+def shape_dataset_names(labels, class_names):
+    return {c: f"{(class_names or {}).get(c, c)}_shapes" for c in labels}
+
+
+def _shaped(res, spacing, labels, class_names, out, group):
+    """the result with 'shapes': every rank takes the shape sums of its slab of every class (_hip.shape_labels, z_base =
+    z0) with the neighbouring ranks' end slices standing for what lies outside it, the tables are merged over the ranks,
+    and rank 0 writes one '<class name>_shapes' dataset per class"""
+    if spacing is None:
+        return res
+    from ..shapes import COLUMNS, gather_tables
+    z0 = int(res['z_range'][0])
+    tables = {}
+    for c in labels:
+        slab = res['volumes'][c].contiguous()
+        below, above = _neighbour_slices(slab, group)
+        tables[c] = gather_tables(_hip.shape_labels(slab, below=below, above=above, z_base=z0), group).cpu().numpy()
+    res['shapes'] = tables
+    res['shape_spacing'] = spacing
+    if out is None:
+        return res
+    names = shape_dataset_names(labels, class_names)
+    missing = _write_tables(out, group, {c: {names[c]: tables[c]} for c in labels},
+                            {c: tables[c].shape[0] for c in labels},
+                            {'shapes': {'columns': list(COLUMNS), 'spacing': list(spacing)}})
+    res['shape_datasets'] = {c: None if c in missing else out[names[c]] for c in labels}
+    return res
+
+
 def _check_mesh(mesh):
     """infer_volume's `mesh` argument -> None or the number of smoothing iterations, before any GPU work"""
     from ..meshes import check
@@ -654,7 +689,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
                  out=None, batch_pixels=None, render_steps=2, group=None, downsample_f=1, pipeline=None,
                  window_slices=None, mem_budget=None, ground_truth=None, compressor=None, pyramid=None,
                  measure=None, split_objects=None, fill_holes=None, morph=None, separate=None, mesh=None,
-                 skeleton=None, contacts=None, thickness=None):
+                 skeleton=None, contacts=None, thickness=None, shapes=None):
     """3D panoptic inference of a (D, H, W) uint8 volume (numpy array, tensor or DeviceVolume) with a 3d engine.
 
     axes: ('xy',) = stack mode, ('xy', 'xz', 'yz') = orthoplane mode with consensus (pdl_inference3d.py:92-96).
@@ -806,6 +841,17 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     as '<class name>_thickness_table' (int64, (m, 3), one raw chunk), the group's attributes gain 'thickness':
     {'columns', 'r_cap', 'cap', 'sampling', 'map': 'squared radius, diameter = 2 sqrt'}, and the result gains
     'thickness_datasets': {class: {'map': array, 'table': array, or None where the store cannot hold a zero-row table}}.
+    shapes: None = no table, no new key, no launch; True, or a voxel spacing (sz, sy, sx) of three positive numbers = once
+    the volumes are final, where measure runs, every rank takes the shape sums of its z-slab of every class on the device
+    (_hip.shape_labels; include/emp_hip.h, E11) with the end slices of the ranks next to it, and the tables are merged
+    over the ranks.  The result gains 'shapes': {class: (n, 26) int64 numpy table of the WHOLE volume, the same on every
+    rank, one row per label ascending: shapes.COLUMNS} -- at most one row (label 1) for a stuff class -- and
+    'shape_spacing': the spacing (True: (1, 1, 1)), which shapes.derive takes to turn the sums into a Crofton surface
+    area, sphericity, the Euler number and the inertia ellipsoid.  The number of tunnels it reports holds for objects that
+    are one 26-connected piece without cavities: ask for split_objects=26 and fill_holes=True.  With out=, rank 0 writes
+    one dataset '<class name>_shapes' per class (int64, (n, 26), one raw chunk), the group's attributes gain 'shapes':
+    {'columns', 'spacing'}, and the result gains 'shape_datasets': {class: array, or None where the store cannot hold a
+    zero-row table}.
     Returns {'volumes': {class: the rank's (z1 - z0, Y, X) device slab}, 'z_range': (z0, z1),
              'instances': {class: number of instances kept}, 'datasets': {class: array or None}}."""
     rank, world = sharded._world(group)
@@ -819,6 +865,7 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
     mesh_iterations = _check_mesh(mesh)
     skeleton = _check_skeleton(skeleton)
     thickness = _check_thickness(thickness)
+    shape_spacing = _check_shapes(shapes)
     levels = None
     if pyramid is not None:
         levels = pyramid_levels(pyramid, tuple(volume.shape), world)[rank]
@@ -891,7 +938,8 @@ def infer_volume(engine, volume, *, norms, labels, axes=('xy', 'xz', 'yz'), merg
         res = _meshed(res, mesh_iterations, thing_list, shape3d, class_names, out, group)
         res = _skeletonized(res, skeleton, thing_list, shape3d, class_names, out, group)
         res = _contacted(res, contacts, class_names, out, group)
-        return _thickened(res, thickness, thing_list, shape3d, class_names, out, group)
+        res = _thickened(res, thickness, thing_list, shape3d, class_names, out, group)
+        return _shaped(res, shape_spacing, labels, class_names, out, group)
 
     if pipeline is not None:
         res = pipeline.run(dv, axes=axes, labels=labels, thing_list=thing_list, params=params, steps=steps, group=group,

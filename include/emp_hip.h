@@ -1204,6 +1204,57 @@ int emp_label_thick_lists(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t h
 int emp_label_thick_resolve(int64_t D, int64_t H, int64_t W, int64_t hb, int64_t ha, int az, int ay, int ax, int cap,
                             const void *work, int64_t work_bytes, uint16_t *out, void *stream);
 
+/* ---- E11: shape descriptors of the labelled objects -- Crofton intercepts, Euler number, second moments -----------------
+ * replaces, on the device, what users of the reference run on a CPU after the fact, object by object: MorphoLibJ's
+ *          "Analyze Regions 3D" or regionprops (surface area, Euler number, inertia ellipsoid).
+ * Setting.  L is a label volume (D, H, W), item = 1 (uint8) or 4 (uint32; the bits of an int32 are taken as they are),
+ *   0 = background; everything outside the volume is 0, as in E2, except the two optional neighbour slices `below`
+ *   (z = -1) and `above` (z = D), contiguous (H, W) arrays of the same item size (null = 0).  A voxel is p = (z, y, x)
+ *   with z counted as z_base + local z.  M(p) is E8's mask of the 26 neighbours of p that carry p's label: bit n stands
+ *   for position 9 (dz + 1) + 3 (dy + 1) + (dx + 1) of the 3 x 3 x 3 block, minus 1 past the centre.
+ * Definition.  The table has one row of 26 int64 per distinct non-zero label, ascending by label as an unsigned
+ *   number; every column after the label is a sum over the voxels p of that label:
+ *     0        label
+ *     1        voxels                   1
+ *     2..4     sum_z, sum_y, sum_x      z, y, x
+ *     5..10    sum_zz, sum_yy, sum_xx, sum_zy, sum_zx, sum_yx     the products of the indices
+ *     11..23   cross_0 .. cross_12      [L(p + d_k) != L(p)] + [L(p - d_k) != L(p)] for E8's edge code k: d_k is the
+ *                                       offset of bit 13 + k of M, i.e. (0,0,1), (0,1,-1), (0,1,0), (0,1,1), (1,-1,-1),
+ *                                       (1,-1,0), (1,-1,1), (1,0,-1), (1,0,0), (1,0,1), (1,1,-1), (1,1,0), (1,1,1)
+ *     24       corners                  the corners (8) of p's unit cube of which p is the first voxel of its label, in
+ *                                       (z, y, x) order, among the 8 voxels around that corner
+ *     25       edges                    the same for the 12 edges of p's cube, with 4 voxels around each
+ *   cross_k counts the ends of the object's intercepts with the lattice lines of direction d_k (two per intercept),
+ *   which is what a Crofton estimate of the surface area needs; background counts as different.  By construction
+ *     - columns 1..4 are E2's voxels, sum_z, sum_y, sum_x, and cross_8, cross_2, cross_0 E2's faces_z, faces_y, faces_x;
+ *     - the object touches faces = 3 voxels + (cross_8 + cross_2 + cross_0) / 2 lattice faces, `corners` lattice points
+ *       and `edges` lattice edges, each counted once: the cells of the cubical complex of its closed voxels;
+ *     - euler = corners - edges + faces - voxels is the Euler number of that complex, i.e. of the object as a
+ *       26-connected set with 6-connected background: the convention of E8 and of E3 with connectivity 26.
+ *   All are sums of integers, so the table of a volume equals the merge (sum per label) of the tables of any
+ *   z-partition whose blocks were given their true neighbour slices, and no visiting order shows in the result.
+ * Limits, refused with EMP_EINVAL before any launch and never truncated: D * H * W <= 2^31 - 1 per call (cut the slab
+ *   into z-blocks), 0 <= z_base, z_base + D <= 2^20, H <= 2^20, W <= 2^20.  The second-order sums are exact while they
+ *   stay below 2^63 -- always at 1024^3, in general while (largest index)^2 * voxels of the label < 2^63.  An overflow
+ *   beyond that wraps and is NOT detected.
+ * Step 1  emp_label_measure_count (E2): the run total n_runs sizes step 2.
+ * Step 2  emp_label_shape_labels: the distinct non-zero labels of the block, ascending, as uint32 in `labels`
+ *         (capacity n_runs); n_out (device int32[1]) receives their number.  work: emp_label_shape_work_bytes(
+ *         n_runs) bytes.
+ * Step 3  emp_label_shape: out_table (n_labels, 26) int64, row i for labels[i]; every cell is written.  One pass over
+ *         the block by tiles of 8 x 8 x 64 voxels; a tile without a label costs the read of its own voxels.  counters
+ *         (device int64[2]): tiles that hold a label, voxels whose sums went to the table directly because their tile
+ *         held more labels than the tile's table has slots.  A label of the block that is missing in `labels` is
+ *         skipped, never written elsewhere.  Integer atomics only: bit-identical from run to run.  n_labels == 0 or
+ *         D == 0 zeroes the counters and returns.                                                                    */
+int64_t emp_label_shape_work_bytes(int64_t n_runs);
+int emp_label_shape_labels(const void *lab, int item, int64_t D, int64_t H, int64_t W, const int32_t *row_offsets,
+                           int64_t n_runs, void *work, int64_t work_bytes, uint32_t *labels, int32_t *n_out,
+                           void *stream);
+int emp_label_shape(const void *lab, int item, int64_t D, int64_t H, int64_t W, const void *below, const void *above,
+                    int64_t z_base, const uint32_t *labels, int64_t n_labels, int64_t *out_table, int64_t *counters,
+                    void *stream);
+
 /* ---- T1 on the device: run table of a plane's slices -> per-instance 3D runs sorted by (instance, start) ------
  * replaces InstanceTracker.update / finish        empanada/inference/tracker.py:61-123
  *          to_coords3d                             empanada/inference/tracker.py:25-38
